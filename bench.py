@@ -7,12 +7,17 @@ tile, the fp32 tiles are gathered to rank 0 over RCCL and assembled.  With N
 GPUs the same image is split N ways (strong scaling).  --config 0..4 selects
 BASELINE.json configs[i] (0 = the 256^2 x 4 spp plumbing run).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Prints one JSON line (rank 0) with the metric, the isect kernel's roofline
-(HIP events on the render stream), the CPU-oracle baseline timed on this
-host, and the parity of the (assembled) image against that oracle render.
+A plain run sets up, warms up, times the K steps and prints one JSON line
+(rank 0) with the metric, ms_per_step and the tracing kernels' roofline from
+the timed steps' own HIP events and device counters.  --dump-outputs DIR
+writes the image the last timed step assembled to DIR/image.npy.  --full adds
+what takes runs of its own: the CPU-oracle baseline timed on this host and the
+parity of the (assembled) image against that oracle render, the stream-copy
+peak beside the roofline, and at N > 1 the other pipeline timed on the same
+tiles.
 """
 from __future__ import annotations
 
@@ -46,6 +51,7 @@ KERNEL_BYTES_PER_CAST = 44     # what isect_queue_kernel moves: ray 24 + meta 4 
 # what render_fused_kernel itself moves per path: its per-sample
 # film write, one escape byte (the reference's unit mode) or an RGB float triple
 FUSED_BYTES_PER_PATH = {True: 1, False: 12}
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: at most this much per run (a larger image is sampled by rows)
 
 
 # BASELINE.json configs (index = position in "configs"); 1 is the headline.
@@ -83,12 +89,20 @@ def parse():
                          "fused for at most two wavefronts of paths)")
     ap.add_argument("--timing-all", action="store_true",
                     help="HIP events around every launch (shade/refill/resolve ms too; costs ~5%% host time)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU-oracle baseline and the image's "
+                         "parity against it (unless --no-cpu-baseline), the stream-copy peak of the roofline, and "
+                         "at N > 1 the other pipeline's leg on the same tiles")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): "
+                         "image.npy, the assembled (3, H, W) image; of an image over the size limit, a fixed seeded "
+                         "sample of its rows")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0 = the CPUs this process may use: affinity mask and cgroup quota)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity")
     ap.add_argument("--no-fused-leg", action="store_true",
-                    help="at N > 1, skip timing the fused pipeline beside the wavefront on the same tiles")
+                    help="with --full at N > 1, skip timing the fused pipeline beside the wavefront on the same tiles")
     ap.add_argument("--save", default="", help="write the rank-0 image (.npy) here")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
@@ -97,6 +111,28 @@ def parse():
             setattr(args, k, cfg[k])
     args.smallpt = cfg["smallpt"]
     return args
+
+
+def writable_scene_dir(scenes):
+    """The generated scenes' cache directory: the package's own (build/scenes
+    under the repository) where this user may write there, else a per-user
+    cache directory, else the temporary directory.  The benchmark also runs
+    from a checkout its user cannot write to; the files are the same
+    wherever they are generated."""
+    import tempfile
+    cands = [scenes.SCENE_DIR,
+             os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"),
+                          "sptamd", "scenes"),
+             os.path.join(tempfile.gettempdir(), f"sptamd-scenes-{os.getuid()}")]
+    for d in cands:
+        try:
+            os.makedirs(d, exist_ok=True)
+            with tempfile.TemporaryFile(dir=d):
+                pass
+            return d
+        except OSError:
+            continue
+    raise RuntimeError("no writable directory for the generated scenes among " + ", ".join(cands))
 
 
 def workload(args, scenes):
@@ -175,6 +211,22 @@ def stream_copy_gbs(torch, dev, nbytes=1 << 30, reps=5):
     return 2.0 * nbytes / (best * 1e-3) / 1e9
 
 
+def dump_outputs(path, image):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step, the assembled (3, H, W) float32 image, as path/image.npy.  An image
+    over DUMP_MAX_BYTES (config 3) is cut to a fixed sample of its rows (seed
+    0, ascending), the same rows in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(image.cpu().numpy(), dtype=np.float32)
+    _, h, w = img.shape
+    keep = DUMP_MAX_BYTES // (3 * w * 4)
+    if keep < h:
+        rows = np.sort(np.random.default_rng(0).choice(h, size=max(1, keep), replace=False))
+        img = np.ascontiguousarray(img[:, rows, :])
+    np.save(os.path.join(path, "image.npy"), img)
+
+
 def cpu_baseline(mesh, args, threads, kw, albedo, emission):
     """Oracle (oracle/, a C restatement of main.cpp:354-446, binned-SAH BVH2,
     one pthread per CPU this process may use) on a bounded row sample of the
@@ -251,7 +303,8 @@ def main():
             dist.init_process_group(backend, timeout=PG_TIMEOUT)
 
     # scene: generated stand-in, loaded through the OBJ reader like main.cpp:365
-    # (rank 0 writes the cached OBJ first)
+    # (rank 0 writes the cached OBJ first), cached where this user may write
+    scenes.SCENE_DIR = writable_scene_dir(scenes)
     if rank == 0 or world == 1:
         src, kw, alb, emi = workload(args, scenes)
     if world > 1:
@@ -410,11 +463,13 @@ def main():
     if paths != W * H * args.spp * args.steps:
         raise RuntimeError(f"device-counted paths {paths} != {W * H * args.spp * args.steps} (W x H x spp x steps)")
     image_main = tg.image.clone() if rank == 0 else None
-    # At N > 1 the fused pipeline is timed beside the wavefront on the same
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, image_main)
+    # With --full at N > 1 the fused pipeline is timed beside the wavefront on the same
     # tiles (a second loop after the first), so the N-GPU line says how the
     # north-star pipeline compares per tile (>= 0.9x).
     other_leg = None
-    if world > 1 and args.pipeline == "auto" and not args.no_fused_leg:
+    if args.full and world > 1 and args.pipeline == "auto" and not args.no_fused_leg:
         other = "wavefront" if st.get("fused") else "fused"
         pw = sptamd.make_params(W, H, args.spp, args.depth, tile_index=rank, tile_count=world, rows_per_group=R,
                                 wavefront_paths=args.wavefront, timing=True, pipeline=other, **kw)
@@ -533,9 +588,10 @@ def main():
                      "note": "SURVEY 8(d) whole-path bytes the per-cast launches would move for these paths, over the "
                              "kernel's busy time; the lane loop keeps them in registers"}
         # whole-path bytes over the whole frame time, against the
-        # spec peak and a stream-copy peak measured here (BASELINE.md plan)
+        # spec peak and (--full: a run of its own) a stream-copy peak measured
+        # here (BASELINE.md plan)
         path_gbs = b_path * paths / elapsed / 1e9
-        copy_gbs = stream_copy_gbs(torch, dev)
+        copy_gbs = stream_copy_gbs(torch, dev) if args.full else None
         build_id = _lib.lib.spt_build_id().decode()
         pmc = pmc_note = None
         key = f"config{args.config}" + ("_fused" if fused else "_drain" if dom_name.endswith("<drain>") else "")
@@ -645,11 +701,11 @@ def main():
                          "build_id": build_id,
                          "valu": valu,
                          "equivalent_wavefront": equiv,
-                         "stream_copy_peak": round(copy_gbs, 1),
+                         "stream_copy_peak": round(copy_gbs, 1) if copy_gbs else None,
                          "path": {"bytes_per_path": round(b_path, 1),
                                   "formula": "84 + 120*S + 60*C (SURVEY 8d), S=%.4f C=%.4f" % (s_bar, c_bar),
                                   "achieved": round(path_gbs, 1), "frac": round(path_gbs / HBM_PEAK_GBS, 4),
-                                  "frac_of_stream_copy": round(path_gbs / copy_gbs, 4)}},
+                                  "frac_of_stream_copy": round(path_gbs / copy_gbs, 4) if copy_gbs else None}},
             "gather_ms": round(gather_ms, 4),
             "kernel_ms_per_step": {k: round(agg[k] / args.steps, 3) for k in
                                    (("isect_ms", "shade_ms", "camera_ms", "resolve_ms") if args.timing_all
@@ -661,7 +717,7 @@ def main():
             rec[other_leg["pipeline"] + "_leg"] = other_leg
         if args.save:
             np.save(args.save, image_main.cpu().numpy())
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0 only, at any world size: the oracle on this host's cores,
             # and the parity of the assembled image (every rank's tile,
             # gathered) against that oracle render; the other ranks wait at

@@ -40,12 +40,12 @@ def test_bench_ranks_match_one_rank(tmp_path, n):
     env.update(SPT_DIST_BACKEND="gloo", SPT_REHEARSE_SHARED_GPU="1")
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", str(n),
-                *SMALL, "--save", str(tmp_path / "n.npy")], env)
+                *SMALL, "--full", "--save", str(tmp_path / "n.npy")], env)
     assert rec["n_gpus"] == n and rec["value"] > 0
     assert rec["dist"] == {"backend": "gloo", "world_size": n}
     assert rec["work_check"]["paths_device_counted"] == rec["work_check"]["expected"] == 256 * 128 * 4
-    # a tile this small (< 2^20 paths) runs fused (AUTO); the other pipeline
-    # is timed beside it on the same tiles, with the same image
+    # a tile this small (< 2^20 paths) runs fused (AUTO); with --full the other
+    # pipeline is timed beside it on the same tiles, with the same image
     assert rec["config"]["pipeline"] == "fused"
     leg = rec["wavefront_leg"]
     assert leg["value"] > 0 and leg["paths_device_counted"] == 256 * 128 * 4 and leg["image_equal"]

@@ -27,7 +27,7 @@ case "${1:-a}" in
   a)
     step tests 700 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread
     step smoke 300 python __graft_entry__.py smoke
-    step bench 400 python bench.py
+    step bench 400 python bench.py --full
     step bench_sync 300 env SPT_BENCH_SYNC=1 python bench.py --steps 10 --warmup 2 --no-cpu-baseline
     step prof 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
         python bench.py --steps 20 --warmup 2 --no-cpu-baseline
@@ -38,7 +38,7 @@ case "${1:-a}" in
     cat $O/prof/timed_window.txt
     ;;
   b)
-    for c in 0 2 3 4; do step bench$c 500 python bench.py --config $c --steps 2 --warmup 1; done
+    for c in 0 2 3 4; do step bench$c 500 python bench.py --full --config $c --steps 2 --warmup 1; done
     if [ "${PMC:-0}" = 1 ]; then
       step pmcd2 600 env CONFIG=2 KERNEL=drain bash tools/pmc_isect.sh $O/pmc
       step pmcd3 600 env CONFIG=3 KERNEL=drain bash tools/pmc_isect.sh $O/pmc

@@ -35,12 +35,12 @@ for s in "$@"; do
     testsgb) run testsgb 900 env SPT_BUILD=gpu python -m pytest tests -m gpu -q -x ;;
     bench4gq) run bench4gq 600 env SPT_BUILD=gpu python bench.py --config 4 --steps 2 --warmup 1 --no-cpu-baseline ;;
     bench1gq) run bench1gq 600 env SPT_BUILD=gpu python bench.py --config 1 --steps 3 --warmup 1 --no-cpu-baseline ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     benchq) run benchq 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline ;;
     bench1x3) for r in 1 2 3; do run bench1_$r 400 python bench.py --steps 20 --warmup 3 --no-cpu-baseline; done ;;
     bench10) run bench10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
     bench1f) run bench1f 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --pipeline fused ;;
-    bench0|bench2|bench3|bench4) run $s 600 python bench.py --config ${s#bench} --steps 2 --warmup 1 ;;
+    bench0|bench2|bench3|bench4) run $s 600 python bench.py --full --config ${s#bench} --steps 2 --warmup 1 ;;
     bench2q|bench3q|bench4q) c=${s#bench}; run $s 600 python bench.py --config ${c%q} --steps 2 --warmup 1 --no-cpu-baseline ;;
     benchwf) for wf in ${WFS:-1048576 4194304 8388608}; do run benchwf$wf 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --wavefront $wf; done ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline ;;
