@@ -516,6 +516,93 @@ spt_status spt_render_async(spt_scene scene, const spt_render_params* params, fl
                             uint64_t* ticket);
 spt_status spt_render_wait(spt_scene scene, uint64_t ticket, spt_render_stats* stats);
 
+/* First-hit feature buffers (AOVs) of a tile, lined up with spt_render's
+ * samples (a build addition: the reference saves one radiance film,
+ * main.cpp:431-433).  Planar, tile_rows x width floats per plane, tile rows in
+ * spt_tile_rows order like the film; each pointer may be NULL on its own to
+ * skip that plane. */
+typedef struct spt_aov {
+    float* albedo_r; float* albedo_g; float* albedo_b;   /* reflectance at the first hit */
+    float* normal_x; float* normal_y; float* normal_z;   /* unit normal, not flipped toward the ray */
+    float* depth;                                        /* the hit's ray parameter t (spt_intersect's) */
+    float* coverage;                                     /* fraction of the pixel's samples that hit */
+} spt_aov;
+
+/* For every pixel of the tile and every sample s in [0, spp): the camera ray
+ * spt_render traces for that (pixel, sample) — the same RNG derivation
+ * (rng_initstate, rng_order, max_depth sets the draws per sample), lens
+ * sampling and tile mapping, so the same ray bit for bit — and its closest hit
+ * (never the any-hit query of a last cast), analytic spheres tested after the
+ * triangles.  A sample that misses is 0 in every plane.  A sample that hits has
+ *   coverage 1;  depth t;
+ *   albedo   the material's reflectance as a bounce multiplies it in: its
+ *            image at the hit's interpolated texcoord (spt_scene_set_texture),
+ *            else its albedo-table colour; a sphere's material is its mat_id,
+ *            a triangle's its material id; ids past the table use material 0;
+ *            mirror and glass materials report their colour like diffuse ones;
+ *   normal   triangles: the interpolated shading normal (w n0 + u n1) + v n2
+ *            (the geometric normal where the normal index is -1), normalised
+ *            as v * (1 / sqrt(v.v)); spheres: normalize((o + t d) - c); (0, 0, 0)
+ *            if its squared length is not a positive finite number.
+ * A pixel's value in each plane is the f32 sum of its samples' values in the
+ * order s = 0 .. spp-1, starting from 0, then / (float)spp: spt_render's
+ * normalisation, independent of how the work is spread over the GPU.  depth
+ * and normal are therefore PREMULTIPLIED by coverage: at a silhouette pixel
+ * divide by coverage for the mean over the hitting samples (a pixel's normal
+ * is in general shorter than 1).  The other fields of params (max_depth apart)
+ * are not used; validation is spt_render's, and `out` NULL or with every
+ * plane NULL is SPT_ERR_INVALID.  The launch runs on `stream` itself, under
+ * the scene mutex, and the setters wait for it like for spt_intersect; it
+ * allocates nothing but (once per spp / max_depth / seed) the RNG jump table
+ * it shares with spt_render. */
+spt_status spt_render_aov(spt_scene scene, const spt_render_params* params, const spt_aov* out, void* stream);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of a whole
+ * image, guided by spt_render_aov's planes (a build addition).  Iteration
+ * i = 0 .. iterations-1 has step 2^i: for pixel p the 5 x 5 taps
+ * q = p + 2^i (dx, dy), dx, dy in [-2, 2], inside the image;
+ *   k = h[|dx|] h[|dy|],  h = {3/8, 1/4, 1/16};   w = k expf(-(e_c + e_n + e_a + e_z)),
+ *   e_c = |c_i(p) - c_i(q)|^2 / (sigma_color 2^-i)^2,   e_n = |n(p) - n(q)|^2 / sigma_normal^2,
+ *   e_a = |a(p) - a(q)|^2 / sigma_albedo^2,   e_z = (z(p) - z(q))^2 / (sigma_depth^2 max(z(p)^2, 1e-12));
+ *   c_{i+1}(p) = sum w c_i(q) / sum w   (the centre tap weighs exactly k(0, 0)).
+ * The normal, albedo and depth are used as spt_render_aov writes them
+ * (premultiplied by coverage; a sky pixel is all zero, so the depth term
+ * separates it from every surface).  A sigma <= 0 disables its term, and so
+ * does a NULL guide plane (the normal and albedo terms need all three of their
+ * planes; guides may be NULL: colour term only).  sigma_depth is relative to
+ * the pixel's own depth. */
+typedef struct spt_denoise_params {
+    uint32_t width, height;
+    uint32_t iterations;        /* 0..8; 0 copies color to out */
+    float sigma_color, sigma_normal, sigma_albedo, sigma_depth;
+} spt_denoise_params;
+
+/* width = height = 0 (set them), 5 iterations (a 125-pixel footprint), and
+ * sigmas chosen on the CPU restatement of the filter (tests/denoise_ref.py)
+ * for low-sample-count renders under the reference's unit sky (env = 1,
+ * albedos <= 1: radiance in [0, 1]): sigma_color 0.6 is in radiance units —
+ * scale it with the image's radiance scale (e.g. x 10 for a sky of 10);
+ * sigma_normal 0.5, sigma_albedo 0.2 and sigma_depth 0.1 (relative) do not
+ * depend on it. */
+void spt_default_denoise_params(spt_denoise_params* p);
+
+/* Bytes of device scratch spt_denoise needs for a width x height image: two
+ * 3-plane images (2 x 3 x 4 x width x height). */
+size_t spt_denoise_scratch_bytes(uint32_t width, uint32_t height);
+
+/* color, out: 3 planes (R, G, B) of width x height floats on the device, as
+ * spt_render's film; out MUST NOT alias color (or scratch).  scratch:
+ * spt_denoise_scratch_bytes(width, height) device bytes, the ping-pong images
+ * of the iterations between the first and the last (may be NULL only when
+ * iterations = 0).  Whole images only (an interleaved row tile has no
+ * neighbours); the call has no scene, never allocates, and queues
+ * `iterations` launches on `stream` (iterations = 0: one copy), the last
+ * writing out.  SPT_ERR_INVALID: NULL params, a zero size, iterations > 8,
+ * NULL color or out, NULL scratch with iterations > 0; SPT_ERR_LIMIT: 2^31
+ * pixels or more.  These checks need no device. */
+spt_status spt_denoise(const spt_denoise_params* p, const float* color, const spt_aov* guides, float* out,
+                       void* scratch, void* stream);
+
 /* The isect kernel's busy time across queued renders (a build addition, for the
  * roofline: renders queued back to back overlap, so per-render busy times do
  * not add up).  After _begin, every SPT_FLAG_TIMING render collected by

@@ -247,10 +247,17 @@ struct JumpTable {
     hipEvent_t write_ev = nullptr;
     hipEvent_t ev[kWorkSets] = {};
     bool ev_used[kWorkSets] = {};
+    // spt_render_aov reads the table on the caller's stream: aov_ev follows its
+    // last launch there (a call on another stream first waits for it, so the
+    // one event covers them all)
+    hipEvent_t aov_ev = nullptr;
+    hipStream_t aov_stream = nullptr;
+    bool aov_used = false;
     void release() {
         hfree(dev);
         if (host) (void)hipHostFree(host);
         if (write_ev) (void)hipEventDestroy(write_ev);
+        if (aov_ev) (void)hipEventDestroy(aov_ev);
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         *this = JumpTable();
     }
@@ -618,6 +625,8 @@ spt_status ensure_jumps(Workspace& w, hipStream_t stream, uint32_t spp, uint32_t
         if (!x.valid ? t->valid : x.lru < t->lru) t = &x;
     for (int k = 0; k < kWorkSets; k++)
         if (t->ev_used[k]) HIP_TRY(hipEventSynchronize(t->ev[k]));  // the renders that read it
+    if (t->aov_used) HIP_TRY(hipEventSynchronize(t->aov_ev));       // and the spt_render_aov calls
+    t->aov_used = false;
     if (t->write_ev) HIP_TRY(hipEventSynchronize(t->write_ev));     // and its last write (staging reuse)
     t->valid = false;
     const size_t n = (size_t)spp + kMaxDepthCasts;
@@ -1942,6 +1951,115 @@ spt_status spt_hit_info_compute(spt_scene sc, const spt_rays* rays, const spt_hi
     a.ntri = sc->ntri;
     HIP_TRY(launch_hit_info(a, (hipStream_t)stream));
     return record_public_use(sc, (hipStream_t)stream);
+}
+
+spt_status spt_render_aov(spt_scene sc, const spt_render_params* pp, const spt_aov* out, void* stream_) {
+    if (!sc || !pp || !out) return fail(SPT_ERR_INVALID, "spt_render_aov: NULL argument");
+    const spt_render_params& p = *pp;
+    // spt_render's checks
+    if (p.width == 0 || p.height == 0 || p.spp == 0 || p.max_depth == 0)
+        return fail(SPT_ERR_INVALID, "spt_render_aov: width/height/spp/max_depth must be > 0");
+    if (p.max_depth > kMaxDepthCasts)
+        return fail(SPT_ERR_LIMIT, "spt_render_aov: max_depth %u > %u", p.max_depth, kMaxDepthCasts);
+    if (p.spp >= (1u << 24)) return fail(SPT_ERR_LIMIT, "spt_render_aov: spp must be < 2^24");
+    if ((uint64_t)p.width * p.height >= (1ull << 31)) return fail(SPT_ERR_LIMIT, "spt_render_aov: image too large");
+    if (p.tile_count == 0 || p.rows_per_group == 0 || p.tile_index >= p.tile_count)
+        return fail(SPT_ERR_INVALID, "spt_render_aov: bad tile (%u of %u, %u rows/group)", p.tile_index, p.tile_count,
+                    p.rows_per_group);
+    if (p.rng_order > 1) return fail(SPT_ERR_INVALID, "spt_render_aov: rng_order must be 0 or 1");
+    if (!out->albedo_r && !out->albedo_g && !out->albedo_b && !out->normal_x && !out->normal_y && !out->normal_z &&
+        !out->depth && !out->coverage)
+        return fail(SPT_ERR_INVALID, "spt_render_aov: every plane is NULL");
+    const hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t rows = spt_tile_rows(p.height, p.tile_index, p.tile_count, p.rows_per_group, nullptr, 0);
+    AovArgs a;
+    a.P = rows * p.width;
+    if (a.P == 0) return SPT_OK;  // an empty tile: nothing to write
+    a.W = p.width;
+    a.spp = p.spp;
+    a.rng_order = p.rng_order;
+    a.tile_index = p.tile_index; a.tile_count = p.tile_count; a.rows_per_group = p.rows_per_group;
+    a.cam = make_camera(p);
+    a.albedo_r = out->albedo_r; a.albedo_g = out->albedo_g; a.albedo_b = out->albedo_b;
+    a.normal_x = out->normal_x; a.normal_y = out->normal_y; a.normal_z = out->normal_z;
+    a.depth = out->depth; a.coverage = out->coverage;
+    // as spt_intersect: a snapshot of the device arrays, launched and recorded
+    // under the mutex (the setters wait for the launch, quiesce_scene)
+    DeviceGuard dg(sc->device);
+    std::lock_guard<std::mutex> lock(sc->mu);
+    a.sc = sc->dev();
+    // the render's own table: the sample jumps depend on max_depth (4 + 2D draws per sample)
+    JumpTable* jtab = nullptr;
+    spt_status st = ensure_jumps(sc->ws, stream, p.spp, p.max_depth, p.rng_initstate, &jtab);
+    if (st) return st;
+    a.sample_jump = jtab->dev;
+    if (!jtab->aov_ev) HIP_TRY(hipEventCreateWithFlags(&jtab->aov_ev, hipEventDisableTiming));
+    if (jtab->aov_used && jtab->aov_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, jtab->aov_ev, 0));
+    HIP_TRY(launch_aov(a, stream));
+    HIP_TRY(hipEventRecord(jtab->aov_ev, stream));
+    jtab->aov_stream = stream;
+    jtab->aov_used = true;
+    return record_public_use(sc, stream);
+}
+
+void spt_default_denoise_params(spt_denoise_params* p) {
+    if (!p) return;
+    p->width = p->height = 0;
+    p->iterations = 5;
+    p->sigma_color = 0.6f;
+    p->sigma_normal = 0.5f;
+    p->sigma_albedo = 0.2f;
+    p->sigma_depth = 0.1f;
+}
+
+size_t spt_denoise_scratch_bytes(uint32_t width, uint32_t height) {
+    return (size_t)2 * 3 * sizeof(float) * (size_t)width * (size_t)height;
+}
+
+spt_status spt_denoise(const spt_denoise_params* pp, const float* color, const spt_aov* guides, float* out,
+                       void* scratch, void* stream_) {
+    if (!pp) return fail(SPT_ERR_INVALID, "spt_denoise: NULL params");
+    const spt_denoise_params& p = *pp;
+    if (p.width == 0 || p.height == 0) return fail(SPT_ERR_INVALID, "spt_denoise: width/height must be > 0");
+    if (p.iterations > 8) return fail(SPT_ERR_INVALID, "spt_denoise: iterations %u > 8", p.iterations);
+    if (!color || !out) return fail(SPT_ERR_INVALID, "spt_denoise: NULL color / out");
+    if (color == out) return fail(SPT_ERR_INVALID, "spt_denoise: out must not alias color");
+    if (p.iterations > 0 && !scratch) return fail(SPT_ERR_INVALID, "spt_denoise: NULL scratch");
+    if ((uint64_t)p.width * p.height >= (1ull << 31)) return fail(SPT_ERR_LIMIT, "spt_denoise: image too large");
+    const hipStream_t stream = (hipStream_t)stream_;
+    const size_t P = (size_t)p.width * p.height;
+    if (p.iterations == 0) {
+        HIP_TRY(hipMemcpyAsync(out, color, 3 * P * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        return SPT_OK;
+    }
+    DenoiseArgs a{};
+    a.width = p.width;
+    a.height = p.height;
+    // 1 / sigma^2, finite (the centre tap's 0 x inf would be NaN); 0: the term is off
+    const auto inv_sq = [](float sigma) { return sigma > 0.0f ? std::min(1.0f / (sigma * sigma), 3.0e38f) : 0.0f; };
+    if (guides && guides->normal_x && guides->normal_y && guides->normal_z) {
+        a.normal_x = guides->normal_x; a.normal_y = guides->normal_y; a.normal_z = guides->normal_z;
+        a.inv_normal = inv_sq(p.sigma_normal);
+    }
+    if (guides && guides->albedo_r && guides->albedo_g && guides->albedo_b) {
+        a.albedo_r = guides->albedo_r; a.albedo_g = guides->albedo_g; a.albedo_b = guides->albedo_b;
+        a.inv_albedo = inv_sq(p.sigma_albedo);
+    }
+    if (guides && guides->depth) {
+        a.depth = guides->depth;
+        a.inv_depth = inv_sq(p.sigma_depth);
+    }
+    float* const ping[2] = {(float*)scratch, (float*)scratch + 3 * P};
+    const float* src = color;
+    for (uint32_t i = 0; i < p.iterations; i++) {
+        a.src = src;
+        a.dst = i + 1 == p.iterations ? out : ping[i & 1u];
+        a.step = 1u << i;
+        a.inv_color = inv_sq(p.sigma_color / (float)(1u << i));  // sigma_color 2^-i
+        HIP_TRY(launch_denoise(a, stream));
+        src = a.dst;
+    }
+    return SPT_OK;
 }
 
 spt_status spt_render_async(spt_scene sc, const spt_render_params* pp, float* film_dev, void* caller_,

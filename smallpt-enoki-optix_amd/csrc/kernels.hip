@@ -1471,6 +1471,88 @@ void camera_cast_kernel(CameraCastArgs a) {
     shade_block<kMode, kSpt, kNt, kIsectBlock>(a.s, valid, c);
 }
 
+// ------------------------------------------------------- first-hit buffers
+// spt_render_aov: the albedo, normal, depth and coverage of every tile pixel's
+// first hits.  One lane per tile pixel: it makes the camera ray of each of the
+// pixel's samples (start_path's arithmetic for that pixel and sample: the
+// render's ray bit for bit), traces its closest hit in lockstep with the
+// wave's other lanes — neighbouring pixels, coherent rays — and adds the
+// sample's features to eight register sums in sample order, so a plane is the
+// f32 sum over s = 0 .. spp-1 from 0, then / (float)spp (the resolve's
+// normalisation), whatever the grid.  A miss adds 0 to every plane; depth and
+// normal are therefore premultiplied by coverage.  No scratch, no second pass.
+// kSpt: the scene has analytic spheres, tested after the triangles as the
+// shade does (material kinds do not matter here: every kind reports its
+// reflectance), so triangle scenes keep the leaner instance.
+template <typename Tr, bool kSpt>
+__global__ __launch_bounds__(kIsectBlock) void aov_kernel(AovArgs a) {
+    extern __shared__ uint32_t lds_stack[];
+    const Lds L = block_lds(lds_stack);
+    const uint32_t p = blockIdx.x * kIsectBlock + threadIdx.x;
+    if (p >= a.P) return;
+    const uint32_t ly = udiv(p, a.W), lx = p - ly * a.W;
+    const uint32_t gy = tile_global_row(ly, a.tile_index, a.tile_count, a.rows_per_group);
+    const uint32_t gpix = gy * a.W + lx;                            // main.cpp:379-382
+    const bool want_albedo = a.albedo_r || a.albedo_g || a.albedo_b;
+    const bool want_normal = a.normal_x || a.normal_y || a.normal_z;
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, dep = 0.0f, cov = 0.0f;
+    for (uint32_t s = 0; s < a.spp; s++) {
+        Pcg32 rng = pcg_start(a.sample_jump[s], (uint64_t)gpix);    // main.cpp:376, then the sample's draws
+        V3 o, d;
+        camera_ray(a.cam, rng, a.rng_order, lx, gy, o, d);
+        NoStats st;
+        Tr tr;
+        tr.init(a.sc, o, d, kRayTmin, kRayTmax, false, L);          // always the closest hit
+        if (!tr.finished())
+            while (!tr.step(a.sc, L, st)) {
+            }
+        TraceHit h = tr.hit(a.sc, L);
+        if (kSpt && a.sc.nsph) trace_spheres(a.sc, o, d, kRayTmin, false, h);
+        V3 rf = v3(0.0f, 0.0f, 0.0f), n = v3(0.0f, 0.0f, 0.0f);
+        float t = 0.0f, c = 0.0f;
+        if (h.slot != -1) {
+            c = 1.0f;
+            t = h.t;
+            const bool sph = kSpt && h.slot < -1;
+            uint32_t mat = 0;
+            V3 sn = v3(0.0f, 0.0f, 0.0f);
+            if (sph) {
+                mat = a.sc.sph_mat ? (uint32_t)a.sc.sph_mat[-2 - h.slot] : 0u;
+                if (want_normal) {  // scatter(): normalize((o + t d) - c)
+                    const float4 sp = a.sc.spheres[-2 - h.slot];
+                    const V3 x = v3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);
+                    sn = v3(x.x - sp.x, x.y - sp.y, x.z - sp.z);
+                }
+            } else {
+                const float4 m0 = a.sc.snrm[(size_t)h.slot * 3];  // n0 + material id
+                mat = f2u(m0.w);
+                if (want_normal) {  // optix_backend.h:483-484, as the shade's phase 2
+                    const float4 m1 = a.sc.snrm[(size_t)h.slot * 3 + 1], m2 = a.sc.snrm[(size_t)h.slot * 3 + 2];
+                    const float w = (1.0f - h.u) - h.v;
+                    sn = v3((w * m0.x + h.u * m1.x) + h.v * m2.x, (w * m0.y + h.u * m1.y) + h.v * m2.y,
+                            (w * m0.z + h.u * m1.z) + h.v * m2.z);
+                }
+            }
+            if (want_albedo) rf = reflectance(a.sc, mat, (uint32_t)h.slot, h.u, h.v);
+            const float len2 = dot(sn, sn);
+            if (want_normal && len2 > 0.0f && len2 < INFINITY) n = normalize(sn);
+        }
+        ar = ar + rf.x; ag = ag + rf.y; ab = ab + rf.z;
+        nx = nx + n.x; ny = ny + n.y; nz = nz + n.z;
+        dep = dep + t;
+        cov = cov + c;
+    }
+    const float fs = (float)a.spp;
+    if (a.albedo_r) a.albedo_r[p] = ar / fs;
+    if (a.albedo_g) a.albedo_g[p] = ag / fs;
+    if (a.albedo_b) a.albedo_b[p] = ab / fs;
+    if (a.normal_x) a.normal_x[p] = nx / fs;
+    if (a.normal_y) a.normal_y[p] = ny / fs;
+    if (a.normal_z) a.normal_z[p] = nz / fs;
+    if (a.depth) a.depth[p] = dep / fs;
+    if (a.coverage) a.coverage[p] = cov / fs;
+}
+
 // ------------------------------------------------------------ fused render
 // The whole of main.cpp:385-426 in one persistent launch per sample chunk:
 // each lane owns one path from its camera ray to termination.  Lanes whose
@@ -2107,6 +2189,22 @@ hipError_t launch_camera_cast(const CameraCastArgs& a, int mode, hipStream_t s) 
                             : launch_camera_cast_m<Tracer8, true>(a, mode, s);
     return a.s.sc.node6 ? launch_camera_cast_m<Tracer6, false>(a, mode, s)
                         : launch_camera_cast_m<Tracer8, false>(a, mode, s);
+}
+
+template <typename Tr>
+static hipError_t launch_aov_t(const AovArgs& a, hipStream_t s) {
+    const size_t lds = (size_t)a.sc.stack_depth * Tr::kStackWords * kIsectBlock * sizeof(uint32_t) + Tr::kExtraLds;
+    const dim3 g(blocks_for(a.P, kIsectBlock)), b(kIsectBlock);
+    if (a.sc.nsph) hipLaunchKernelGGL((aov_kernel<Tr, true>), g, b, lds, s, a);
+    else hipLaunchKernelGGL((aov_kernel<Tr, false>), g, b, lds, s, a);
+    return hipGetLastError();
+}
+
+// every tree width; a.P: the tile's pixels (one lane each)
+hipError_t launch_aov(const AovArgs& a, hipStream_t s) {
+    if (a.P == 0) return hipSuccess;
+    if (!a.sc.nodes8) return launch_aov_t<Tracer>(a, s);
+    return a.sc.node6 ? launch_aov_t<Tracer6>(a, s) : launch_aov_t<Tracer8>(a, s);
 }
 
 hipError_t launch_isect_queue_stats(const IsectQueueArgs& a, uint32_t grid_items, hipStream_t s) {

@@ -20,6 +20,14 @@
 //   spt_render_cli [scene.obj|scene.pbrt|scene.sptc] [-w W] [-h H] [-s spp] [-d casts] [-o out.pfm]
 //                  [--wavefront paths] [--rr depth] [--rng-x-first] [--device N] [--save-cache f.sptc]
 //                  [--gpus N] [--rows-per-group R] [--rehearse-shared-gpu]
+//                  [--aov PREFIX] [--denoise [--denoise-iters N]]
+//
+// --aov PREFIX writes the first-hit buffers of the render (spt_render_aov) as
+// PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm (depth in all three
+// channels) and PREFIX.coverage.pfm.  --denoise filters the image with
+// spt_denoise (default sigmas, --denoise-iters iterations) guided by those
+// buffers: the denoised image goes to -o, the raw one to <out>.raw.pfm.
+// Single-device only: neither combines with --gpus above 1.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -196,7 +204,9 @@ void render_multi(const std::string& path, const spt::Mesh* mesh, spt_render_par
 int main(int argc, char** argv) {
     std::string obj = "mitsuba.obj";  // main.cpp:365
     std::string out = "wurst.pfm";    // main.cpp:442
-    std::string cache_out;
+    std::string cache_out, aov_prefix;
+    bool do_denoise = false;
+    int denoise_iters = -1;  // -1: spt_default_denoise_params
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
     bool shared = false;
@@ -222,10 +232,24 @@ int main(int argc, char** argv) {
         else if (a == "--gpus") ngpu = std::atoi(next());
         else if (a == "--rows-per-group") rows_per_group = (uint32_t)std::atoi(next());
         else if (a == "--rehearse-shared-gpu") shared = true;
+        else if (a == "--aov") aov_prefix = next();
+        else if (a == "--denoise") do_denoise = true;
+        else if (a == "--denoise-iters") denoise_iters = std::atoi(next());
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
     }
     if (ngpu < 0 || rows_per_group == 0) { std::cerr << "--gpus must be >= 1, --rows-per-group >= 1\n"; return 2; }
+    const bool want_aov = !aov_prefix.empty() || do_denoise;
+    if (want_aov && ngpu > 1) {
+        std::cerr << "--aov / --denoise render on one device: not with --gpus " << ngpu
+                  << " (the multi-GPU gather of the feature buffers is not implemented)\n";
+        return 2;
+    }
+    if (denoise_iters > 8 || (denoise_iters >= 0 && !do_denoise)) {
+        std::cerr << "--denoise-iters takes 0..8 and goes with --denoise\n";
+        return 2;
+    }
+    if (want_aov && ngpu == 1) ngpu = 0;  // one tile: the single-device path below (the same image)
     try {
         const bool cache = spt::ends_with(obj, ".sptc");
         std::unique_ptr<spt::Mesh> mesh;
@@ -276,6 +300,34 @@ int main(int argc, char** argv) {
             ms = ms_since(t0);
             std::cout << ms << std::endl;  // main.cpp:431
             hip_check(hipMemcpy(host.data(), film, sizeof(float) * 3 * npx, hipMemcpyDeviceToHost), "hipMemcpy film");
+            if (want_aov) {
+                spt::AovBuffers aov(npx);
+                scene.render_aov(p, aov.planes());
+                if (!aov_prefix.empty()) {
+                    const std::vector<float> a = aov.to_host();  // albedo r g b, normal x y z, depth, coverage
+                    const float* d = a.data();
+                    auto write = [&](const char* name, const float* r, const float* g, const float* b) {
+                        spt::check(spt_pfm_write((aov_prefix + name).c_str(), r, g, b, p.width, p.height), "spt_pfm_write");
+                    };
+                    write(".albedo.pfm", d, d + npx, d + 2 * npx);
+                    write(".normal.pfm", d + 3 * npx, d + 4 * npx, d + 5 * npx);
+                    write(".depth.pfm", d + 6 * npx, d + 6 * npx, d + 6 * npx);
+                    write(".coverage.pfm", d + 7 * npx, d + 7 * npx, d + 7 * npx);
+                }
+                if (do_denoise) {
+                    spt::check(spt_pfm_write((out + ".raw.pfm").c_str(), host.data(), host.data() + npx,
+                                             host.data() + 2 * npx, p.width, p.height),
+                               "spt_pfm_write");
+                    spt_denoise_params dp;
+                    spt_default_denoise_params(&dp);
+                    dp.width = p.width;
+                    dp.height = p.height;
+                    if (denoise_iters >= 0) dp.iterations = (uint32_t)denoise_iters;
+                    spt::DeviceFloats clean(3 * npx);
+                    spt::denoise(dp, film, &aov.planes(), clean.get());
+                    host = clean.to_host();
+                }
+            }
             (void)hipFree(film);
         }
         std::cout << "writing image" << std::endl;  // main.cpp:441

@@ -3,6 +3,8 @@
 // optix_backend.h:25-66) and its Scene / backend call shape
 // (Scene::add_triangle_mesh / commit / intersect, main.cpp:286-352).
 #pragma once
+#include <hip/hip_runtime_api.h>
+
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -85,6 +87,10 @@ class Scene {
     void render(const spt_render_params& p, float* film_dev, spt_render_stats* stats, void* stream = nullptr) {
         check(spt_render(scene_, &p, film_dev, stats, stream), "spt_render");
     }
+    // spt_render_aov: the first-hit buffers of p's tile, queued on `stream`
+    void render_aov(const spt_render_params& p, const spt_aov& planes, void* stream = nullptr) {
+        check(spt_render_aov(scene_, &p, &planes, stream), "spt_render_aov");
+    }
     // Commit a mesh loaded elsewhere (read only: several devices' scenes may
     // be built from one host mesh, one thread per device).
     void commit_from(const Mesh& mesh, int device) {
@@ -104,5 +110,57 @@ class Scene {
     spt_pbrt_info pbrt_{};
     spt_scene scene_ = nullptr;
 };
+
+// Device floats owned for a scope (hipMalloc / hipFree; throws like check()).
+class DeviceFloats {
+  public:
+    explicit DeviceFloats(size_t n) : n_(n) {
+        if (hipMalloc((void**)&p_, sizeof(float) * (n ? n : 1)) != hipSuccess)
+            throw std::runtime_error("hipMalloc of " + std::to_string(n) + " floats failed");
+    }
+    ~DeviceFloats() { (void)hipFree(p_); }
+    DeviceFloats(const DeviceFloats&) = delete;
+    DeviceFloats& operator=(const DeviceFloats&) = delete;
+    float* get() const { return p_; }
+    size_t size() const { return n_; }
+    std::vector<float> to_host() const {  // synchronises with the null stream's order
+        std::vector<float> h(n_);
+        if (n_ && hipMemcpy(h.data(), p_, sizeof(float) * n_, hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("hipMemcpy to the host failed");
+        return h;
+    }
+
+  private:
+    float* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// The eight planes of spt_render_aov for a tile of npx pixels, in one
+// allocation: albedo r g b, normal x y z, depth, coverage.
+class AovBuffers {
+  public:
+    explicit AovBuffers(size_t npx) : npx_(npx), buf_(8 * npx) {
+        float* b = buf_.get();
+        aov_ = spt_aov{b, b + npx, b + 2 * npx, b + 3 * npx, b + 4 * npx, b + 5 * npx, b + 6 * npx, b + 7 * npx};
+    }
+    const spt_aov& planes() const { return aov_; }
+    size_t pixels() const { return npx_; }
+    std::vector<float> to_host() const { return buf_.to_host(); }  // 8 x npx, in the order above
+
+  private:
+    size_t npx_;
+    DeviceFloats buf_;
+    spt_aov aov_{};
+};
+
+// spt_denoise with its scratch allocated for the call: color, out = 3 planes of
+// p.width x p.height device floats (out must not alias color); guides may be
+// NULL.  Synchronises `stream` before the scratch is freed.
+inline void denoise(const spt_denoise_params& p, const float* color, const spt_aov* guides, float* out,
+                    void* stream = nullptr) {
+    DeviceFloats scratch(spt_denoise_scratch_bytes(p.width, p.height) / sizeof(float));
+    check(spt_denoise(&p, color, guides, out, scratch.get(), stream), "spt_denoise");
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) throw std::runtime_error("spt::denoise: stream failed");
+}
 
 }  // namespace spt

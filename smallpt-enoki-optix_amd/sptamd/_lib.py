@@ -37,6 +37,7 @@ EXPORTED = [
     "spt_scene_save", "spt_scene_load", "spt_scene_cache_info",
     "spt_scene_isect_busy_begin", "spt_scene_isect_busy_end", "spt_scene_kernel_busy",
     "spt_debug_fail_workspace_alloc",
+    "spt_render_aov", "spt_default_denoise_params", "spt_denoise_scratch_bytes", "spt_denoise",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -148,6 +149,20 @@ class PbrtInfo(ctypes.Structure):
                 ("shapes_skipped", c_uint64), ("instances", c_uint64)]
 
 
+AOV_PLANES = ("albedo_r", "albedo_g", "albedo_b", "normal_x", "normal_y", "normal_z", "depth", "coverage")
+
+
+class Aov(ctypes.Structure):
+    """spt_aov: the first-hit planes of spt_render_aov / the guides of spt_denoise."""
+    _fields_ = [(n, c_void_p) for n in AOV_PLANES]
+
+
+class DenoiseParams(ctypes.Structure):
+    _fields_ = [("width", c_uint32), ("height", c_uint32), ("iterations", c_uint32),
+                ("sigma_color", c_float), ("sigma_normal", c_float), ("sigma_albedo", c_float),
+                ("sigma_depth", c_float)]
+
+
 def _load() -> ctypes.CDLL:
     # torch ships its own HIP runtime (SONAME libamdhip64.so.7).  Load it first
     # so libspt.so binds to that one copy: loading libspt.so first would map the
@@ -196,6 +211,10 @@ def _load() -> ctypes.CDLL:
         "spt_scene_save": (i32, [vp, c_char_p, vp, u64]),
         "spt_scene_load": (i32, [c_char_p, POINTER(vp), vp, u64, POINTER(u64)]),
         "spt_scene_cache_info": (i32, [c_char_p, POINTER(SceneStats), POINTER(Config), POINTER(u64)]),
+        "spt_render_aov": (i32, [vp, POINTER(RenderParams), POINTER(Aov), vp]),
+        "spt_default_denoise_params": (None, [POINTER(DenoiseParams)]),
+        "spt_denoise_scratch_bytes": (ctypes.c_size_t, [u32, u32]),
+        "spt_denoise": (i32, [POINTER(DenoiseParams), vp, POINTER(Aov), vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -215,6 +234,12 @@ def check(status: int, what: str) -> None:
 def default_params() -> RenderParams:
     p = RenderParams()
     lib.spt_default_params(ctypes.byref(p))
+    return p
+
+
+def default_denoise_params() -> DenoiseParams:
+    p = DenoiseParams()
+    lib.spt_default_denoise_params(ctypes.byref(p))
     return p
 
 
@@ -317,7 +342,7 @@ def tile_rows(height: int, tile_index: int, tile_count: int, rows_per_group: int
 
 __all__ = [
     "lib", "check", "SptError", "Rays", "Hits", "HitInfo", "Camera", "RenderParams", "RenderStats",
-    "SceneStats", "Mesh", "Config", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
+    "SceneStats", "Mesh", "Config", "Aov", "AOV_PLANES", "DenoiseParams", "default_denoise_params", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
     "LIB_PATH", "REPO_ROOT",
     "PCG32_DEFAULT_STATE", "SPT_RNG_Y_FIRST", "SPT_RNG_X_FIRST", "SPT_FLAG_TIMING", "c_uint8",
 ]

@@ -461,6 +461,36 @@ class Scene:
         check(lib.spt_render_wait(self.backend.handle, ticket, ctypes.byref(st)), "spt_render_wait")
         return st.as_dict()
 
+    def render_aov(self, params: RenderParams, planes: Sequence[str] = ("albedo", "normal", "depth", "coverage"),
+                   stream=None, out: Optional[dict] = None) -> dict:
+        """spt_render_aov: the first-hit buffers of params' tile, lined up with
+        render(params)'s samples.  planes: any of "albedo", "normal" ((3, rows,
+        W) float32 device tensors), "depth", "coverage" ((rows, W)); the others
+        are not computed.  Depth and normal are premultiplied by coverage
+        (include/spt.h).  out: tensors to fill instead of new ones, by name.
+        Queued on `stream` (default: torch's current stream), not waited for."""
+        rows = _lib.tile_row_count(params.height, params.tile_index, params.tile_count, params.rows_per_group)
+        res, aov = {}, _lib.Aov()
+        for name in planes:
+            if name not in ("albedo", "normal", "depth", "coverage"):
+                raise ValueError(f"render_aov: unknown plane {name!r}")
+            shape = (3, rows, params.width) if name in ("albedo", "normal") else (rows, params.width)
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=torch.float32, device=self.backend.device)
+            assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == shape, name
+            res[name] = t
+            if name in ("albedo", "normal"):
+                for c, field in enumerate(("albedo_r", "albedo_g", "albedo_b") if name == "albedo"
+                                          else ("normal_x", "normal_y", "normal_z")):
+                    setattr(aov, field, t[c].data_ptr())
+            else:
+                setattr(aov, name, t.data_ptr())
+        self.backend.sync_config()
+        check(lib.spt_render_aov(self.backend.handle, ctypes.byref(params), ctypes.byref(aov),
+                                 _stream_handle(stream)), "spt_render_aov")
+        return res
+
     def isect_busy_begin(self) -> None:
         """spt_scene_isect_busy_begin: start collecting isect launch intervals."""
         check(lib.spt_scene_isect_busy_begin(self.backend.handle), "spt_scene_isect_busy_begin")
@@ -488,6 +518,55 @@ class Scene:
             film = torch.empty((3, rows, params.width), dtype=torch.float32, device=self.backend.device)
         assert film.is_contiguous() and film.numel() >= 3 * rows * params.width
         return film
+
+
+def aov_struct(aov: Optional[dict]) -> _lib.Aov:
+    """spt_aov over render_aov's dict (missing names: NULL planes)."""
+    a = _lib.Aov()
+    for name, fields in (("albedo", ("albedo_r", "albedo_g", "albedo_b")), ("normal", ("normal_x", "normal_y", "normal_z"))):
+        t = None if aov is None else aov.get(name)
+        if t is not None:
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == 3, name
+            for c, f in enumerate(fields):
+                setattr(a, f, t[c].data_ptr())
+    for name in ("depth", "coverage"):
+        t = None if aov is None else aov.get(name)
+        if t is not None:
+            assert t.is_contiguous() and t.dtype == torch.float32, name
+            setattr(a, name, t.data_ptr())
+    return a
+
+
+def denoise(film: torch.Tensor, aov: Optional[dict] = None, iterations: int = 5, sigma_color: Optional[float] = None,
+            sigma_normal: Optional[float] = None, sigma_albedo: Optional[float] = None,
+            sigma_depth: Optional[float] = None, stream=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """spt_denoise: the edge-avoiding a-trous filter of a whole (3, H, W) film,
+    guided by render_aov's dict (a missing plane disables its term).  Sigmas
+    default to spt_default_denoise_params (sigma_color assumes radiance in
+    [0, 1]); <= 0 disables a term.  Scratch and the result come from torch; the
+    launches are queued on `stream` (default: the current stream)."""
+    assert film.is_cuda and film.is_contiguous() and film.dtype == torch.float32 and film.dim() == 3 and \
+        film.shape[0] == 3, "film must be a contiguous (3, H, W) float32 device tensor"
+    p = _lib.default_denoise_params()
+    p.height, p.width, p.iterations = int(film.shape[1]), int(film.shape[2]), iterations
+    for k, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo),
+                 ("sigma_depth", sigma_depth)):
+        if v is not None:
+            setattr(p, k, float(v))
+    for name in ("albedo", "normal", "depth"):
+        t = None if aov is None else aov.get(name)
+        assert t is None or tuple(t.shape[-2:]) == tuple(film.shape[1:]), f"{name}: not the film's size"
+    s = stream if stream is not None else torch.cuda.current_stream(film.device)
+    with torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty_like(film)
+        scratch = torch.empty(max(1, lib.spt_denoise_scratch_bytes(p.width, p.height)), dtype=torch.uint8,
+                              device=film.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == film.shape
+    guides = aov_struct(aov)
+    check(lib.spt_denoise(ctypes.byref(p), film.data_ptr(), ctypes.byref(guides), out.data_ptr(), scratch.data_ptr(),
+                          s.cuda_stream or None), "spt_denoise")
+    return out
 
 
 def scene_cache_info(path: str) -> dict:
