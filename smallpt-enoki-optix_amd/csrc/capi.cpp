@@ -112,18 +112,9 @@ struct Counters {
     alignas(128) uint32_t isect_next; // persistent isect work counter (zeroed by each refill)
     uint32_t exhausted;  // RefillArgs::iter_tag of the refill that started the last work item (0: not yet)
     uint32_t pad[2];
-    alignas(128) uint32_t isect_next_b;  // SPT_ISECT_CAMERA: the counter of the launches on queue 1
     alignas(128) uint32_t xcd_next[8][32];  // the drain / fused kernel's per-XCD work counters (one line each)
     alignas(128) uint32_t surv_shard[kShards][kShardStride];  // a sharded camera cast's survivors per shard
 };
-uint32_t* isect_next_of(Counters* c, int queue) { return queue ? &c->isect_next_b : &c->isect_next; }
-
-// Camera paths started inside the isect launches (no refill launch per
-// iteration): an experiment, VERDICT r3 item 3 (EXPERIMENTS.md round 4).
-#ifndef SPT_ISECT_CAMERA
-#define SPT_ISECT_CAMERA 0
-#endif
-constexpr bool kIsectCam = SPT_ISECT_CAMERA != 0;
 
 // Render-wide device statistics.
 struct Stats {
@@ -2379,9 +2370,8 @@ retry_fit:
     RefillArgs ra[kMaxStreams];
     FusedArgs da[kMaxStreams];   // the drain launches (launch_drain)
     uint32_t drain_T[kMaxStreams] = {};
-    // the drain: not with traversal counters (isect kernel only) or camera
-    // paths started inside the isect launches (an experiment)
-    const bool drain_on = cfg.drain_q8 != 0 && !trav_stats && !kIsectCam;
+    // the drain: not with traversal counters (isect kernel only)
+    const bool drain_on = cfg.drain_q8 != 0 && !trav_stats;
     // spt_config.xcd_remap bit 2: XCD-aware work distribution in the lane loops (drain, fused)
     const bool lane_xcd = (cfg.xcd_remap & 4u) != 0;
     // spt_config.drain_sort: a forced drain takes its queue sorted (wide-BVH scenes)
@@ -2563,11 +2553,9 @@ retry_fit:
             sub_end[k] = we;
             started[k] = wb + first;
             lock0[k] = cfg.lockstep_first && fit && drain_on && !trav_stats && first >= drain_T[k];
-            // (SPT_ISECT_CAMERA: the first isect launch starts these paths; the
-            // camera cast makes them itself: the refill only keeps the books)
+            // (the camera cast makes these paths itself: the refill only keeps the books)
             ra[k].book_only = lock0[k] && cam_cast ? 1u : 0u;
-            if (!kIsectCam &&
-                (st = mark(0, strm[k], [&] { return launch_refill(ra[k], ra[k].book_only ? 1u : first, strm[k]); })))
+            if ((st = mark(0, strm[k], [&] { return launch_refill(ra[k], ra[k].book_only ? 1u : first, strm[k]); })))
                 return st;
             ra[k].book_only = 0;
         }
@@ -2612,24 +2600,6 @@ retry_fit:
                     const int c = cur[k], nx = 1 - c;
                     ia[k].q = q[k][c];
                     ia[k].count = &b.cnt->qn[c];
-                    const bool cam = kIsectCam && !trav_stats;
-                    if (cam) {
-                        // survivors in q[c] (surv[c]) plus new camera paths after
-                        // them; the previous launch (queue nx) left its cursor in
-                        // cursor[nx]; this one's shade appends to surv[nx]
-                        RefillArgs& R = ia[k].cam;
-                        R = ra[k];
-                        R.q = q[k][c];
-                        R.surv = &b.cnt->surv[c];
-                        R.cursor_in = it == 0 ? nullptr : &b.cnt->cursor[nx];
-                        R.cursor_out = &b.cnt->cursor[c];
-                        R.qn_out = &b.cnt->qn[c];
-                        R.isect_next = isect_next_of(b.cnt, nx);
-                        R.surv_clear = &b.cnt->surv[nx];
-                        R.casts_in = nullptr;
-                        R.iter_tag = (uint32_t)it + 1;
-                        ia[k].next = isect_next_of(b.cnt, c);
-                    }
                     // The drain phase: once the stream's last work items are (about
                     // to be) started — the host's view lags one or two batches, in
                     // which the cursor moves < kDrainLookahead capacities — a drain
@@ -2642,8 +2612,12 @@ retry_fit:
                     // drain_casts after the exhausting refill (limit - max_depth) the
                     // drain runs whatever the queue holds, and the stream ends: no
                     // work is left to start, so nothing can enter its queue again
-                    const bool force = dph && cfg.drain_casts && limit[k] != UINT64_MAX &&
-                                       it + p.max_depth >= limit[k] + cfg.drain_casts;
+                    // (both `force` and the camera cast's `sharded` below depend on this)
+                    const auto forced_at = [&](int sub, uint64_t iter) {
+                        return drain_on && cfg.drain_casts && limit[sub] != UINT64_MAX &&
+                               iter + p.max_depth >= limit[sub] + cfg.drain_casts;
+                    };
+                    const bool force = forced_at(k, it);
                     ia[k].drain_below = force ? 0xffffffffu : dph ? drain_T[k] : 0u;
                     sa[k].drain_below = ia[k].drain_below;
                     if (force) {
@@ -2682,7 +2656,7 @@ retry_fit:
                         // the first cast, camera ray to shade, in one launch; survivors
                         // into queue nx (surv[nx] zeroed with the counters), the
                         // refill below keeps the books as after a shade
-                        sharded = cam_shards && started[k] >= sub_end[k] && cfg.drain_casts == 1 && !drain_sort;
+                        sharded = cam_shards && !drain_sort && forced_at(k, it + 1);
                         CameraCastArgs ca;
                         ca.r = ra[k];  // the first refill's work items (cursor_init: the share's start)
                         ca.s = sa[k];
@@ -2703,8 +2677,7 @@ retry_fit:
                     } else if ((st = mark(1, strm[k], [&] {
                              if (lockstep) return launch_isect_lockstep(ia[k], known[k], strm[k]);
                              return trav_stats ? launch_isect_queue_stats(ia[k], known[k], strm[k])
-                                               : cam ? launch_isect_queue_cam(ia[k], known[k], strm[k])
-                                                     : launch_isect_queue(ia[k], known[k], strm[k]);
+                                               : launch_isect_queue(ia[k], known[k], strm[k]);
                          })))
                         return st;
                     // surv[nx] was zeroed by the previous refill (surv_clear)
@@ -2723,10 +2696,6 @@ retry_fit:
                         da[k].perm = nullptr;
                         if ((st = mark(4, strm[k], [&] { return launch_drain(da[k], mode, strm[k]); }))) return st;
                         drain_launches++;
-                    }
-                    if (cam) {  // no refill launch: the next isect starts the new paths
-                        cur[k] = nx;
-                        continue;
                     }
                     ra[k].q = q[k][nx]; ra[k].surv = &b.cnt->surv[nx]; ra[k].cursor_in = &b.cnt->cursor[c];
                     ra[k].cursor_out = &b.cnt->cursor[nx]; ra[k].qn_out = &b.cnt->qn[nx];
@@ -2765,19 +2734,8 @@ retry_fit:
                 if (pending[k] >= 0) {
                     HIP_TRY(hipEventSynchronize(b.count_ev[pending[k]]));
                     const Counters& hc = b.host_cnt[pending[k]];
-                    if (kIsectCam && !trav_stats) {
-                        // after an isect on queue 1 - pend_cur and its shade into
-                        // pend_cur: the next launch holds those survivors plus as
-                        // many new paths as fit
-                        const uint32_t sv = hc.surv[pend_cur[k]];
-                        const uint64_t cu = hc.cursor[1 - pend_cur[k]];
-                        started[k] = std::max<uint64_t>(started[k], cu);
-                        const uint64_t left = sub_end[k] > started[k] ? sub_end[k] - started[k] : 0;
-                        known[k] = (uint32_t)std::min<uint64_t>(ws.sub[k].cap, sv + left);
-                    } else {
-                        known[k] = hc.qn[pend_cur[k]];
-                        started[k] = std::max<uint64_t>(started[k], hc.cursor[pend_cur[k]]);
-                    }
+                    known[k] = hc.qn[pend_cur[k]];
+                    started[k] = std::max<uint64_t>(started[k], hc.cursor[pend_cur[k]]);
                     if (known[k] == 0) {
                         live[k] = false;
                         nlive--;

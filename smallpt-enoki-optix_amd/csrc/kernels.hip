@@ -15,16 +15,7 @@ namespace spt {
 // scalar: the compiler cannot tell that threadIdx.x >> 6 or a value shuffled
 // from lane 0 is uniform, and would otherwise keep the work-pool state in
 // VGPRs and branch on it per lane.
-#ifndef SPT_UNIFORM
-#define SPT_UNIFORM 1
-#endif
-__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) {
-#if SPT_UNIFORM
-    return __builtin_amdgcn_readfirstlane(v);
-#else
-    return v;
-#endif
-}
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Path-queue and hit-record accesses: each element is written once and read
 // once per cast.  kNt (spt_config.queue_cache): non-temporal, so they leave
@@ -90,26 +81,15 @@ __device__ __forceinline__ void stq2(float2* p, float2 x) {
 #define SPT_DRAIN_WAVES 7
 #endif
 // the albedo / emitter drains at 6 (80 VGPRs, 32 B of scratch with the path's
-// throughput and radiance parked in LDS, SPT_PARK_PATH) instead of the fused
-// kernel's 5: config 2 +1.7 % (profiles/r05_exp/fit_paths_rgb_waves/), parking
-// +2.5 % more (profiles/r05_exp/park_path/); 7 waves (64 B of scratch) no better
-// albedo / emitter lane loops keep a path's throughput and radiance in LDS
-// while its ray traces (render_fused_kernel)
-#ifndef SPT_PARK_PATH
-#define SPT_PARK_PATH 1
-#endif
+// throughput and radiance parked in LDS, render_fused_kernel's kPark) instead
+// of the fused kernel's 5: config 2 +1.7 % (profiles/r05_exp/fit_paths_rgb_waves/),
+// parking +2.5 % more (profiles/r05_exp/park_path/); 7 waves (64 B of scratch) no better
 #ifndef SPT_DRAIN_WAVES_RGB
 #define SPT_DRAIN_WAVES_RGB 6
 #endif
 #ifndef SPT_DRAIN_WAVES_NT
 #define SPT_DRAIN_WAVES_NT 6
 #endif
-// lane loops (render_fused_kernel): continued and refilled lanes set up their
-// new rays in one tr.init after the refill instead of one each
-#ifndef SPT_MERGED_INIT
-#define SPT_MERGED_INIT 1
-#endif
-
 // Diagnostic build only (make BUILD=build_wlog EXTRA=-DSPT_WAVE_LOG=1,
 // tools/wave_log.py): every wave of a lane-loop launch (fused kernel, drain)
 // records its start and end on the 100-MHz wall clock, the HW_ID / XCC_ID
@@ -201,7 +181,6 @@ __device__ __forceinline__ void trace_spheres(const DeviceScene& sc, V3 o, V3 d,
 }
 
 struct NoStats {
-    __device__ void empty_visit() {}
     __device__ void node() {}
     __device__ void tri() {}
     __device__ void step() {}
@@ -209,9 +188,8 @@ struct NoStats {
     __device__ void wave_blocks(bool, bool) {}
 };
 struct TravStats {
-    uint32_t nodes = 0, tris = 0, steps = 0, max_sp = 0, empties = 0;
+    uint32_t nodes = 0, tris = 0, steps = 0, max_sp = 0;
     uint32_t tri_waves = 0, node_waves = 0;  // wave steps that ran the triangle / the visit block
-    __device__ void empty_visit() { empties++; }
     __device__ void node() { nodes++; }
     __device__ void tri() { tris++; }
     __device__ void step() { steps++; }
@@ -372,38 +350,30 @@ struct Tracer {
 // (the margin is formed as one mul and one fma: it bounds the rounding of the
 // slab form with several ulps to spare, so its own rounding does not matter)
 constexpr float kMarginRel = 1e-6f;
-// Step modes (template argument of Tracer8T): 0 = one triangle test OR one
-// node visit per step; 1 = the last triangle of a group rides along with the
-// next node visit; 2 = as 1 with a second triangle-group slot, so a node visit
-// rides along with any triangle test while that slot is free.
-#ifndef SPT_MERGED_STEP
-#define SPT_MERGED_STEP 2
-#endif
-#ifndef SPT_FUSED_STEP
-#define SPT_FUSED_STEP 2
-#endif
-#ifndef SPT_EARLY_DONE
-#define SPT_EARLY_DONE 1
-#endif
+// A step tests at most one triangle and visits at most one node (step()); a
+// second triangle-group slot lets a node visit ride along with any triangle
+// test while that slot is free.
 constexpr float kMinDir = 1e-20f;
 
-// kLds: the per-ray Woop constants (Sx, Sy, Sz, axis indices) and the hit
-// record (slot, id, u, v) live in LDS, one 16-B record each per lane after the
-// stack (ds_read_b128 / ds_write_b128, conflict-free), not in VGPRs; only the
-// hit distance stays in a register (every box test reads it).
+// The per-ray Woop constants (Sx, Sy, Sz, axis indices) and the hit record
+// (slot, u, v) live in LDS, one 16-B record each per lane after the stack
+// (ds_read_b128 / ds_write_b128, conflict-free), not in VGPRs; only the hit
+// distance stays in a register (every box test reads it).
 //
 // kW = 6: the 64-B node of bvh_build.h (at most six children; one 64-B
 // half-line per visit, four loads instead of five; same hit-bit scheme).
 //
-// kDefer (with kLds): the hit record keeps the un-divided barycentrics and
-// the divides run once per ray (the fused kernel: +2.6 %; the isect kernel,
-// which finishes a ray about as often as it accepts a hit: -0.7 %).
-template <int kStep, bool kLds, int kW = 8, bool kDefer = false>
+// kDefer: the hit record keeps the un-divided barycentrics and the divides
+// run once per ray (the fused kernel: +2.6 %; the isect kernel, which
+// finishes a ray about as often as it accepts a hit: -0.7 %).
+template <int kW = 8, bool kDefer = false>
 struct Tracer8T {
     static constexpr uint32_t kQuads = kW == 6 ? kNode6Quads : kNode8Quads;
     // the 64-B node's visit fits 64 VGPRs: 8 waves per SIMD where the LDS
     // stack allows it (the 80-B node's spills there)
     static constexpr int kMinWaves = kW == 6 ? SPT_ISECT_WAVES6 : SPT_ISECT_WAVES;
+    // written by init only (the rest reads the LDS copy, wrec); a member all the
+    // same: as a local of init the lane loops' registers are allocated otherwise
     WoopRay wr;
     V3 o;
     float ix, iy, iz, tmin, tbox;
@@ -416,12 +386,12 @@ struct Tracer8T {
     // (word << group_shift) + s, gpu_bvh8_holes) — one word, also one LDS stack entry
     uint32_t nhits;
     uint32_t tbase, thits;
-    uint32_t tbase2, thits2;  // kStep 2: a second triangle group, queued behind (tbase, thits)
+    uint32_t tbase2, thits2;  // a second triangle group, queued behind (tbase, thits)
     uint32_t spa;  // byte offset of this lane's stack top in the block's LDS: tid * 4 + depth * 512
     bool anyhit, done;
-    TraceHit h;
+    float ht;  // the distance of the hit kept so far (the rest of it: hrec)
     static constexpr uint32_t kStackWords = 1;
-    static constexpr uint32_t kExtraLds = kLds ? 2 * kIsectBlock * 16 : 0;
+    static constexpr uint32_t kExtraLds = 2 * kIsectBlock * 16;
     static constexpr uint32_t kRow = kIsectBlock * 4;  // bytes per stack level
     __device__ __forceinline__ bool finished() const { return done; }
 
@@ -438,11 +408,10 @@ struct Tracer8T {
     // original id is read back from the triangle record (the isect queue
     // kernel writes the slot and never asks for it).
     __device__ __forceinline__ TraceHit hit(const DeviceScene& sc, const Lds& L) const {
-        if constexpr (!kLds) return h;
         const uint4 r = *hrec(sc, L);
         TraceHit x;
         x.slot = (int32_t)r.x;
-        x.t = h.t;
+        x.t = ht;
         if (r.x == 0xffffffffu) {
             x.id = 0xffffffffu; x.u = 0.0f; x.v = 0.0f;
         } else if constexpr (!kDefer) {
@@ -466,15 +435,13 @@ struct Tracer8T {
         o = o_;
         wr = woop_setup(o_, d);
         spa = (L.wbase + lane_id()) * 4u;
-        if constexpr (kLds) {
-            *wrec(sc, L) = make_uint4(f2u(wr.Sx), f2u(wr.Sy), f2u(wr.Sz), wr.k);
-            // "no hit": slot -1, id ~0 (materialised here: a constant vector
-            // hoisted out of the ray loop would occupy four VGPRs throughout)
-            uint32_t none, zero;
-            asm volatile("v_mov_b32 %0, -1" : "=v"(none));
-            asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
-            *hrec(sc, L) = make_uint4(none, none, zero, zero);
-        }
+        *wrec(sc, L) = make_uint4(f2u(wr.Sx), f2u(wr.Sy), f2u(wr.Sz), wr.k);
+        // "no hit": slot -1, id ~0 (materialised here: a constant vector
+        // hoisted out of the ray loop would occupy four VGPRs throughout)
+        uint32_t none, zero;
+        asm volatile("v_mov_b32 %0, -1" : "=v"(none));
+        asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+        *hrec(sc, L) = make_uint4(none, none, zero, zero);
         const float dx = fabsf(d.x) < kMinDir ? copysignf(kMinDir, d.x) : d.x;
         const float dy = fabsf(d.y) < kMinDir ? copysignf(kMinDir, d.y) : d.y;
         const float dz = fabsf(d.z) < kMinDir ? copysignf(kMinDir, d.z) : d.z;
@@ -494,13 +461,7 @@ struct Tracer8T {
         tbase2 = 0;
         thits2 = 0;
         done = sc.empty != 0;
-        h.slot = -1; h.id = 0xffffffffu; h.t = tmax_; h.u = 0.0f; h.v = 0.0f;
-    }
-
-    __device__ __forceinline__ void visit(const DeviceScene& sc, uint32_t node) {
-        const uint4* np = sc.nodes8 + (size_t)node * kQuads;
-        if constexpr (kW == 6) visit_words6(np[0], np[1], np[2], np[3]);
-        else visit_words(np[0], np[1], np[2], np[3], np[4]);
+        ht = tmax_;
     }
 
     // inner children's meta bytes 0b001_11sss (24 + slot) take the ray's
@@ -514,12 +475,10 @@ struct Tracer8T {
 
     __device__ __forceinline__ void take_hits(uint32_t hm, uint32_t group, uint32_t tri_base) {
         nhits = (hm & 0xff000000u) | group;
-        if constexpr (kStep >= 2) {
-            if (thits) {  // the current group still has triangles: queue the new one
-                tbase2 = tri_base;
-                thits2 = hm & 0x00ffffffu;
-                return;
-            }
+        if (thits) {  // the current group still has triangles: queue the new one
+            tbase2 = tri_base;
+            thits2 = hm & 0x00ffffffu;
+            return;
         }
         tbase = tri_base;
         thits = hm & 0x00ffffffu;
@@ -560,7 +519,7 @@ struct Tracer8T {
             const float tez = fmaf((float)(((lo ? ezl : e45z) >> sh) & 0xffu), az, bze);
             const float txz = fmaf((float)(((lo ? xzl : e45z) >> (lo ? sh : sh + 16u)) & 0xffu), az, bzx);
             const float tn = fmaxf(fmaxf(tex, tey), fmaxf(tez, tbox));
-            const float tf = fminf(fminf(txx, txy), fminf(txz, h.t));
+            const float tf = fminf(fminf(txx, txy), fminf(txz, ht));
             const uint32_t mw = lo ? mlo : mhi;
             const uint32_t bits = __builtin_amdgcn_ubfe(mw, sh + 5u, 3u) << __builtin_amdgcn_ubfe(mw, sh, 5u);
             hm = (tn <= tf) ? (hm | bits) : hm;
@@ -599,7 +558,7 @@ struct Tracer8T {
             const float tez = fmaf((float)(((lo ? ezl : ezh) >> sh) & 0xffu), az, bze);
             const float txz = fmaf((float)(((lo ? xzl : xzh) >> sh) & 0xffu), az, bzx);
             const float tn = fmaxf(fmaxf(tex, tey), fmaxf(tez, tbox));
-            const float tf = fminf(fminf(txx, txy), fminf(txz, h.t));
+            const float tf = fminf(fminf(txx, txy), fminf(txz, ht));
             const uint32_t mw = lo ? mlo : mhi;
             const uint32_t bits = __builtin_amdgcn_ubfe(mw, sh + 5u, 3u) << __builtin_amdgcn_ubfe(mw, sh, 5u);
             hm = (tn <= tf) ? (hm | bits) : hm;
@@ -610,64 +569,44 @@ struct Tracer8T {
     // P0..P2: the slot's vertices loaded rotated by rot() (f: the record + rot)
     __device__ __forceinline__ bool tri_test(const DeviceScene& sc, V3 P0, V3 P1, V3 P2, const float* f, uint32_t s,
                                              const Lds& L, const uint4 wk) {
-        float t, u, v;
+        float t;
         WoopRay wl;
         wl.o = o;
-        if constexpr (kLds) { wl.Sx = u2f(wk.x); wl.Sy = u2f(wk.y); wl.Sz = u2f(wk.z); wl.k = wk.w; }
-        else wl = wr;
+        wl.Sx = u2f(wk.x); wl.Sy = u2f(wk.y); wl.Sz = u2f(wk.z); wl.k = wk.w;
         const V3 O = rot_origin();
-        if constexpr (kLds) {
-            uint4* hr = hrec(sc, L);
-            if constexpr (!kDefer) {
-                if (woop_test_rot(wl, O, P0, P1, P2, TriReload{f}, tmin, h.t, t, u, v)) {
-                    // accepted means t <= h.t; a tie goes to the smaller original
-                    // id (both read from the triangle records: rare)
-                    bool take = t < h.t;
-                    if (!take) {
-                        const uint32_t cs = hr->x;
-                        take = cs == 0xffffffffu || tri_id(sc, s) < tri_id(sc, cs);
-                    }
-                    if (take) {
-                        h.t = t;
-                        *hr = make_uint4((uint32_t)s, 0u, f2u(u), f2u(v));
-                    }
-                    return true;
-                }
-                return false;
-            }
-            float V, W, det;
-            if (woop_test_raw_rot(wl, O, P0, P1, P2, TriReload{f}, tmin, h.t, t, V, W, det)) {
-                bool take = t < h.t;
+        uint4* hr = hrec(sc, L);
+        if constexpr (!kDefer) {
+            float u, v;
+            if (woop_test_rot(wl, O, P0, P1, P2, TriReload{f}, tmin, ht, t, u, v)) {
+                // accepted means t <= ht; a tie goes to the smaller original
+                // id (both read from the triangle records: rare)
+                bool take = t < ht;
                 if (!take) {
                     const uint32_t cs = hr->x;
                     take = cs == 0xffffffffu || tri_id(sc, s) < tri_id(sc, cs);
                 }
                 if (take) {
-                    h.t = t;
-                    *hr = make_uint4((uint32_t)s, f2u(V), f2u(W), f2u(det));
+                    ht = t;
+                    *hr = make_uint4((uint32_t)s, 0u, f2u(u), f2u(v));
                 }
                 return true;
             }
             return false;
         }
-        if (woop_test_rot(wl, O, P0, P1, P2, TriReload{f}, tmin, h.t, t, u, v)) {
-            const uint32_t id = tri_id(sc, s);
-            if (t < h.t || id < h.id) {
-                h.t = t;
-                h.id = id;
-                h.slot = (int32_t)s;
-                h.u = u;
-                h.v = v;
+        float V, W, det;
+        if (woop_test_raw_rot(wl, O, P0, P1, P2, TriReload{f}, tmin, ht, t, V, W, det)) {
+            bool take = t < ht;
+            if (!take) {
+                const uint32_t cs = hr->x;
+                take = cs == 0xffffffffu || tri_id(sc, s) < tri_id(sc, cs);
+            }
+            if (take) {
+                ht = t;
+                *hr = make_uint4((uint32_t)s, f2u(V), f2u(W), f2u(det));
             }
             return true;
         }
         return false;
-    }
-
-    template <typename Stats>
-    __device__ __forceinline__ bool step(const DeviceScene& sc, const Lds& L, Stats& stats) {
-        if constexpr (kStep == 0) return step_single(sc, L, stats);
-        else return step_merged(sc, L, stats);
     }
 
     // One step = at most one triangle test and one node visit, their loads in
@@ -676,20 +615,17 @@ struct Tracer8T {
     // so most triangle tests cost no dependent memory round trip of their own.
     // The visit culls against the hit the triangle test just made.
     template <typename Stats>
-    __device__ __forceinline__ bool step_merged(const DeviceScene& sc, const Lds& L, Stats& stats) {
+    __device__ __forceinline__ bool step(const DeviceScene& sc, const Lds& L, Stats& stats) {
         stats.step();
-        if constexpr (kStep >= 2) {
-            if (!thits) {
-                tbase = tbase2;
-                thits = thits2;
-                thits2 = 0u;
-            }
+        if (!thits) {
+            tbase = tbase2;
+            thits = thits2;
+            thits2 = 0u;
         }
         const bool has_tri = thits != 0u;
         const bool has_node = (nhits & 0xff000000u) != 0u || spa >= kRow;
         if (!has_tri && !has_node) { done = true; return true; }
-        const bool do_node = kStep >= 2 ? has_node && thits2 == 0u     // a free slot for the visit's triangles
-                                        : has_node && (thits & (thits - 1u)) == 0u;
+        const bool do_node = has_node && thits2 == 0u;  // a free slot for the visit's triangles
         // loads are unconditional (idle sides read slot / node 0, always
         // cached) so both sets are in flight before either is waited on
         const uint32_t s = has_tri ? tbase + (uint32_t)__builtin_ctz(thits) : 0u;
@@ -698,8 +634,11 @@ struct Tracer8T {
         const float* f = tri_rec(sc, s) + rot();
         V3 P0, P1, P2;
         tri_vertices(f, P0, P1, P2);
+        // (zeroed, then assigned: written so the compiler narrows the read to
+        // the 12 B the triangle test uses, ds_read_b96; as one copy-constructed
+        // uint4 it reads all 16 B and allocates registers differently)
         uint4 wk = make_uint4(0u, 0u, 0u, 0u);
-        if constexpr (kLds) wk = *wrec(sc, L);
+        wk = *wrec(sc, L);
         if (do_node && !(nhits & 0xff000000u)) {
             spa -= kRow;
             nhits = *stack_top(L);
@@ -723,65 +662,20 @@ struct Tracer8T {
         if constexpr (kW != 6) w4 = np[4];
         if (has_tri && tri_test(sc, P0, P1, P2, f, s, L, wk) && anyhit) { done = true; return true; }
         if (do_node) {
-            const uint32_t tb = thits | thits2;
             if constexpr (kW == 6) visit_words6(w0, w1, w2, w3);
             else visit_words(w0, w1, w2, w3, w4);
-            if (!(nhits & 0xff000000u) && (thits | thits2) == tb) stats.empty_visit();  // no child box hit
         }
-#if SPT_EARLY_DONE
         // nothing left (no triangles, no hit children, empty stack): finish
         // now rather than in a step of its own, so the lane is idle (and can
         // be refilled) one step sooner
         if (!(thits | thits2 | (nhits & 0xff000000u)) && spa < kRow) { done = true; return true; }
-#endif
-        return false;
-    }
-
-    template <typename Stats>
-    __device__ __forceinline__ bool step_single(const DeviceScene& sc, const Lds& L, Stats& stats) {
-        stats.step();
-        if (thits) {
-            stats.tri();
-            const uint32_t s = tbase + (uint32_t)__builtin_ctz(thits);
-            thits &= thits - 1u;
-            const float* f = tri_rec(sc, s) + rot();
-            V3 P0, P1, P2;
-            tri_vertices(f, P0, P1, P2);
-            uint4 wk = make_uint4(0u, 0u, 0u, 0u);
-            if constexpr (kLds) wk = *wrec(sc, L);
-            if (tri_test(sc, P0, P1, P2, f, s, L, wk) && anyhit) { done = true; return true; }
-            return false;
-        }
-        if (!(nhits & 0xff000000u)) {
-            // current group exhausted: pop the next one (stacked groups always
-            // hold inner children) and visit its nearest child in this step
-            if (spa < kRow) { done = true; return true; }
-            spa -= kRow;
-            nhits = *stack_top(L);
-        }
-        stats.node();
-        const uint32_t bit = 31u - (uint32_t)__builtin_clz(nhits);
-        const uint32_t child = ((nhits & 0x00ffffffu) << sc.group_shift) + (((bit - 24u) ^ oct_rep) & 7u);
-        nhits &= ~(1u << bit);
-        if (nhits & 0xff000000u) {
-            *stack_top(L) = nhits;
-            spa += kRow;
-            stats.push(spa / kRow);
-        }
-        visit(sc, child);
         return false;
     }
 };
-#ifndef SPT_LDS_RAY
-#define SPT_LDS_RAY 1
-#endif
-using Tracer8 = Tracer8T<SPT_MERGED_STEP, SPT_LDS_RAY>;  // isect kernels
-using Tracer6 = Tracer8T<SPT_MERGED_STEP, SPT_LDS_RAY, 6>;  // isect kernels, 64-B nodes
-#ifndef SPT_FUSED_LDS
-#define SPT_FUSED_LDS 1
-#endif
-using Tracer8F = Tracer8T<SPT_FUSED_STEP, SPT_FUSED_LDS, 8, true>;  // fused trace+shade kernel
-using Tracer6F = Tracer8T<SPT_FUSED_STEP, SPT_FUSED_LDS, 6, true>;
+using Tracer8 = Tracer8T<8>;         // isect kernels
+using Tracer6 = Tracer8T<6>;         // isect kernels, 64-B nodes
+using Tracer8F = Tracer8T<8, true>;  // fused trace+shade kernel
+using Tracer6F = Tracer8T<6, true>;
 
 template <typename Tr, typename Stats = NoStats>
 __device__ __forceinline__ TraceHit trace(const DeviceScene& sc, V3 o, V3 d, float tmin, float tmax,
@@ -819,39 +713,14 @@ __device__ __forceinline__ void start_path(const RefillArgs& r, uint64_t w, V3& 
     meta = s << kMetaDepthBits;
 }
 
-#ifndef SPT_ISECT_CAM_WAVES
-#define SPT_ISECT_CAM_WAVES 8
-#endif
-template <typename Tr, bool kStats, bool kCam = false, bool kNt = false>
+template <typename Tr, bool kStats, bool kNt = false>
 __global__ __launch_bounds__(kIsectBlock)
-__attribute__((amdgpu_waves_per_eu(kStats ? 1 : (kCam ? SPT_ISECT_CAM_WAVES : Tr::kMinWaves), 8)))
+__attribute__((amdgpu_waves_per_eu(kStats ? 1 : Tr::kMinWaves, 8)))
 void isect_queue_kernel(IsectQueueArgs a) {
     extern __shared__ uint32_t lds_stack[];
     const Lds L = block_lds(lds_stack);
-    uint32_t n, nq = 0;
-    uint64_t cur = 0;
-    if constexpr (kCam) {
-        // survivors in [0, nq), new camera paths in [nq, n) (refill_kernel's rule)
-        nq = wave_uniform(*a.cam.surv);
-        cur = a.cam.cursor_in ? *a.cam.cursor_in : a.cam.cursor_init;
-        const uint64_t avail = a.cam.work_end > cur ? a.cam.work_end - cur : 0;
-        const uint32_t room = a.cam.capacity - nq;
-        const uint32_t total = (uint32_t)(avail < room ? avail : room);
-        n = nq + total;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            *a.cam.cursor_out = cur + total;
-            *a.cam.qn_out = n;
-            *a.cam.isect_next = 0;  // the next launch's work counter
-            *a.cam.surv_clear = 0;  // the shade after this launch appends survivors there
-            if (cur < a.cam.work_end && cur + total >= a.cam.work_end) *a.cam.exhausted = a.cam.iter_tag;
-            if (n) atomicAdd(&a.cam.stats[0], (unsigned long long)n);       // casts
-            if (nq) atomicAdd(&a.cam.stats[1], (unsigned long long)nq);     // continuations
-            if (total) atomicAdd(&a.cam.stats[2], (unsigned long long)total);  // camera paths started
-        }
-    } else {
-        n = *a.count;
-        if (n < a.drain_below) return;  // the drain launch after the shade takes this queue
-    }
+    const uint32_t n = *a.count;
+    if (n < a.drain_below) return;  // the drain launch after the shade takes this queue
     typename std::conditional<kStats, TravStats, NoStats>::type st;
     Tr tr;
     uint32_t ray = 0;
@@ -883,23 +752,9 @@ void isect_queue_kernel(IsectQueueArgs a) {
                 const uint32_t take = min((uint32_t)__popcll(idle), pool_end - pool);
                 if (!busy && rank < take) {
                     ray = pool + rank;
-                    V3 o, d;
-                    uint32_t depth;
-                    if (!kCam || ray < nq) {
-                        const float4 q1 = ldq<kNt>(a.q.q1 + ray), q2 = ldq<kNt>(a.q.q2 + ray);
-                        o = v3(q1.x, q1.y, q1.z);
-                        d = v3(q2.x, q2.y, q2.z);
-                        depth = f2u(q1.w) & ((1u << kMetaDepthBits) - 1u);
-                    } else {
-                        // a new camera path: its ray is made here and stored for the shade
-                        uint32_t p, meta;
-                        start_path(a.cam, cur + (ray - nq), o, d, p, meta);
-                        stq<kNt>(a.q.q1 + ray, make_float4(o.x, o.y, o.z, u2f(meta)));
-                        stq<kNt>(a.q.q2 + ray, make_float4(d.x, d.y, d.z, u2f(p)));
-                        if (a.cam.mode >= kModeAlbedo) stq<kNt>(a.q.q0 + ray, make_float4(1.0f, 1.0f, 1.0f, 0.0f));
-                        if (a.cam.mode == kModeEmit) stq2<kNt>(a.q.rad + ray, make_float2(0.0f, 0.0f));
-                        depth = 0;
-                    }
+                    const float4 q1 = ldq<kNt>(a.q.q1 + ray), q2 = ldq<kNt>(a.q.q2 + ray);
+                    const V3 o = v3(q1.x, q1.y, q1.z), d = v3(q2.x, q2.y, q2.z);
+                    const uint32_t depth = f2u(q1.w) & ((1u << kMetaDepthBits) - 1u);
                     // any-hit for the last cast unless emitters need the surface
                     tr.init(a.sc, o, d, kRayTmin, kRayTmax, depth + 1 >= a.max_depth && !a.sc.emission, L);
                     busy = !tr.finished();
@@ -927,11 +782,7 @@ void isect_queue_kernel(IsectQueueArgs a) {
         if ((threadIdx.x & 63u) == 0) atomicAdd(&a.trav_stats[3], (unsigned long long)wave_steps);
         atomicAdd(&a.trav_stats[5], (unsigned long long)st.tri_waves);
         atomicAdd(&a.trav_stats[6], (unsigned long long)st.node_waves);
-#if SPT_EMPTY_VISIT_STAT
-        atomicAdd(&a.trav_stats[4], (unsigned long long)st.empties);  // experiment: visits with no child hit
-#else
         atomicMax(&a.trav_stats[4], (unsigned long long)st.max_sp);
-#endif
     }
 }
 
@@ -1107,13 +958,7 @@ __device__ __forceinline__ Pcg32 path_rng(uint32_t gpix, const PcgJump& js, cons
 // instead of one thread per queue slot the host may have to fill (the host
 // sizes it before it knows how many paths ended): config 1 +0.9 %, config 2
 // +1.8 % (profiles/r03_tune/knob_sweep.log).
-#ifndef SPT_REFILL_STRIDE
-#define SPT_REFILL_STRIDE 1
-#endif
-#ifndef SPT_REFILL_MAX_BLOCKS
-#define SPT_REFILL_MAX_BLOCKS 4096
-#endif
-constexpr uint32_t kRefillMaxBlocks = SPT_REFILL_MAX_BLOCKS;
+constexpr uint32_t kRefillMaxBlocks = 4096;
 template <int kMode, bool kNt = false>
 __global__ __launch_bounds__(256) void refill_kernel(RefillArgs a) {
     uint32_t surv = 0;
@@ -1142,13 +987,7 @@ __global__ __launch_bounds__(256) void refill_kernel(RefillArgs a) {
         if (total) atomicAdd(&a.stats[2], (unsigned long long)total);
     }
     if (a.book_only) return;
-#if SPT_REFILL_STRIDE
     for (uint32_t j = i; j < total; j += gridDim.x * 256u) {
-#else
-    if (i >= total) return;
-    {
-        const uint32_t j = i;
-#endif
         uint32_t s, q, lx, ly;
         work_item((uint32_t)(cur + j - (uint64_t)a.chunk_s0 * a.P), a.chunk_s0, a.chunk_ns, a.P, a.work_order != 0, s,
                   q);
@@ -1164,9 +1003,6 @@ __global__ __launch_bounds__(256) void refill_kernel(RefillArgs a) {
 }
 
 // ----------------------------------------------------------------- shade
-#ifndef SPT_OCT_GROUP
-#define SPT_OCT_GROUP 0
-#endif
 // main.cpp:404-425 for one cast of every queued path.  A path that ends
 // writes its contribution once per (sample, pixel): unit mode one byte
 // (escaped or not: the sky term is added in sample order by the resolve),
@@ -1372,27 +1208,7 @@ __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, cons
         }
     }
     __syncthreads();
-    uint32_t slot_in_wave = rank;
-#if SPT_OCT_GROUP
-    // a wave's survivors in the order of their bounce direction's octant (then
-    // lane order): the drain's lanes take consecutive queue entries, so rays
-    // refilled together start out heading the same way (order only: the same
-    // paths, the same bits)
-    {
-        const uint32_t oct = emit ? (nd.x < 0.0f ? 1u : 0u) | (nd.y < 0.0f ? 2u : 0u) | (nd.z < 0.0f ? 4u : 0u) : 8u;
-        uint32_t before = 0, mine = 0;
-#pragma unroll
-        for (uint32_t o = 0; o < 8u; o++) {
-            const uint64_t b = __ballot(oct == o);
-            const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-            if (oct == o) mine = before + r;
-            before += (uint32_t)__popcll(b);
-        }
-        slot_in_wave = mine;
-    }
-#endif
-    if (emit)
-        store_path<kMode, kNt>(a.out, s_wave_off[wave] + slot_in_wave, no, nd, pix, meta + 1u, tr, tg, tb, lr, lg, lb);
+    if (emit) store_path<kMode, kNt>(a.out, s_wave_off[wave] + rank, no, nd, pix, meta + 1u, tr, tg, tb, lr, lg, lb);
 }
 
 template <int kMode, bool kSpt, bool kNt = false>
@@ -1408,12 +1224,6 @@ __global__ __launch_bounds__(kShadeBlock) void shade_kernel(ShadeArgs a) {
 }
 
 // ----------------------------------------------------------- camera cast
-#ifndef SPT_CAM_RECOMPUTE
-#define SPT_CAM_RECOMPUTE 0
-#endif
-#ifndef SPT_CAM_WAVES
-#define SPT_CAM_WAVES 0  // 0: the tracer's (8 for the 64-B node)
-#endif
 // A fitting job's first cast in one launch (spt_config.camera_cast): one lane
 // per work item of the sub-wavefront — its camera ray (refill_kernel's
 // arithmetic, start_path), its trace in lockstep with the wave's other lanes
@@ -1434,8 +1244,7 @@ struct CamSrc {  // the path in registers: its first cast, just traced
     __device__ __forceinline__ float2 rad() const { return make_float2(0.0f, 0.0f); }
 };
 template <typename Tr, int kMode, bool kSpt, bool kNt>
-__global__ __launch_bounds__(kIsectBlock)
-__attribute__((amdgpu_waves_per_eu(SPT_CAM_WAVES ? SPT_CAM_WAVES : Tr::kMinWaves, 8)))
+__global__ __launch_bounds__(kIsectBlock) __attribute__((amdgpu_waves_per_eu(Tr::kMinWaves, 8)))
 void camera_cast_kernel(CameraCastArgs a) {
     extern __shared__ uint32_t lds_stack[];
     const Lds L = block_lds(lds_stack);
@@ -1458,15 +1267,6 @@ void camera_cast_kernel(CameraCastArgs a) {
             while (!tr.step(a.s.sc, L, st)) {
             }
         c.h = tr.hit(a.s.sc, L);
-#if SPT_CAM_RECOMPUTE
-        // the ray again (the same arithmetic, the same bits) rather than keeping
-        // its direction, pixel and sample live across the traversal: the
-        // traversal keeps its 64 VGPRs (8 waves) with no spill.  The opaque
-        // copy of the work item stops the compiler from reusing the first one.
-        uint32_t w = i;
-        asm volatile("" : "+v"(w));
-        start_path(a.r, a.r.cursor_init + w, c.o, c.d, c.pix, c.meta);
-#endif
     }
     shade_block<kMode, kSpt, kNt, kIsectBlock>(a.s, valid, c);
 }
@@ -1577,7 +1377,6 @@ __attribute__((amdgpu_waves_per_eu(kDrain && kMode == kModeUnit ? (kNt ? SPT_DRA
                                    : kDrain ? SPT_DRAIN_WAVES_RGB : SPT_FUSED_WAVES, 8)))
 void render_fused_kernel(FusedArgs a) {
     constexpr bool kEmit = kMode == kModeEmit;
-    constexpr bool kMergedInit = SPT_MERGED_INIT != 0;
 #if SPT_WAVE_LOG
     const unsigned long long wl_t0 = (unsigned long long)wall_clock64();
 #endif
@@ -1613,7 +1412,7 @@ void render_fused_kernel(FusedArgs a) {
     // albedo / emitter modes: a lane's throughput and gathered radiance wait in
     // LDS while its ray traces (two float4 per lane after the tracer's records),
     // so the traversal loop does not hold them in VGPRs
-    constexpr bool kPark = kMode != kModeUnit && SPT_PARK_PATH;
+    constexpr bool kPark = kMode != kModeUnit;
     float4* const park = kPark ? (float4*)((char*)L.base + a.sc.stack_depth * kIsectBlock * 4u + Tr::kExtraLds) +
                                      2u * threadIdx.x
                                : nullptr;
@@ -1649,7 +1448,7 @@ void render_fused_kernel(FusedArgs a) {
             // ---- shade every pending lane (shade_kernel, main.cpp:404-425)
             casts += (uint32_t)__popcll(__ballot(pending));
             bool cont = false;
-            bool need_init = false;  // kMergedInit: a new ray in tr.o / dir to set up after the refill
+            bool need_init = false;  // a new ray in tr.o / dir to set up after the refill
             if (pending) {
                 pending = false;
                 bool term = true;
@@ -1726,12 +1525,8 @@ void render_fused_kernel(FusedArgs a) {
                                 park[0] = make_float4(thr, thg, thb, lr);
                                 park[1] = make_float4(lg, lb, 0.0f, 0.0f);
                             }
-                            if constexpr (kMergedInit) {
-                                tr.o = hp;  // traced from here: set up below with the refilled lanes
-                                need_init = true;
-                            } else {
-                                tr.init(a.sc, hp, dir, kRayTmin, kRayTmax, depth + 2 >= a.max_depth && !kEmit, L);
-                            }
+                            tr.o = hp;  // traced from here: set up below with the refilled lanes
+                            need_init = true;
                             busy = true;
                             cont = true;
                         }
@@ -1795,7 +1590,6 @@ void render_fused_kernel(FusedArgs a) {
                     const uint32_t j = a.perm ? a.perm[pool + rank] : pool + rank;
                     const float4 q1 = ldq<kNt>(a.q.q1 + j), q2 = ldq<kNt>(a.q.q2 + j);
                     meta = f2u(q1.w);
-                    const uint32_t depth = meta & ((1u << kMetaDepthBits) - 1u);
                     pix = f2u(q2.w);
                     dir = v3(q2.x, q2.y, q2.z);
                     thr = thg = thb = 1.0f;
@@ -1814,17 +1608,8 @@ void render_fused_kernel(FusedArgs a) {
                         park[1] = make_float4(lg, lb, 0.0f, 0.0f);
                     }
                     busy = true;
-                    if constexpr (kMergedInit) {
-                        tr.o = v3(q1.x, q1.y, q1.z);
-                        need_init = true;
-                    } else {
-                        tr.init(a.sc, v3(q1.x, q1.y, q1.z), dir, kRayTmin, kRayTmax, depth + 1 >= a.max_depth && !kEmit,
-                                L);
-                        if (tr.finished()) {  // empty scene: a miss
-                            busy = false;
-                            pending = true;
-                        }
-                    }
+                    tr.o = v3(q1.x, q1.y, q1.z);
+                    need_init = true;
                 } else if (!kDrain && !busy && !pending && rank < take) {
                     uint32_t sample;
                     work_item(pool + rank, a.sample0, a.pm_ns, a.P, a.pm_ns != 0, sample, pix);  // work0 = sample0 * P
@@ -1842,16 +1627,8 @@ void render_fused_kernel(FusedArgs a) {
                         park[1] = make_float4(lg, lb, 0.0f, 0.0f);
                     }
                     busy = true;
-                    if constexpr (kMergedInit) {
-                        tr.o = o;
-                        need_init = true;
-                    } else {
-                        tr.init(a.sc, o, dir, kRayTmin, kRayTmax, a.max_depth <= 1 && !kEmit, L);
-                        if (tr.finished()) {  // empty scene: a miss
-                            busy = false;
-                            pending = true;
-                        }
-                    }
+                    tr.o = o;
+                    need_init = true;
                 }
                 if (!kDrain) starts += take;
                 pool += take;
@@ -1860,7 +1637,7 @@ void render_fused_kernel(FusedArgs a) {
 #endif
                 idle = __ballot(!busy && !pending);
             }
-            if (kMergedInit && need_init) {
+            if (need_init) {
                 // one ray set-up for the continued and the refilled lanes (one
                 // copy of the code instead of two); the last cast of a path is
                 // an any-hit query (unit mode)
@@ -2079,7 +1856,7 @@ __global__ __launch_bounds__(256) void hit_info_kernel(HitInfoArgs a) {
 static inline uint32_t blocks_for(uint32_t items, uint32_t block) { return (items + block - 1) / block; }
 
 // Workgroups resident on the whole chip for this LDS stack size (cached).
-template <typename Tr, bool kStats, bool kCam, bool kNt>
+template <typename Tr, bool kStats, bool kNt>
 static uint32_t persistent_blocks(size_t lds) {
     static thread_local size_t cached_lds = 0;
     static thread_local uint32_t cached = 0;
@@ -2088,7 +1865,7 @@ static uint32_t persistent_blocks(size_t lds) {
     (void)hipGetDevice(&dev);
     if (cached && cached_lds == lds && cached_dev == dev) return cached;
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, isect_queue_kernel<Tr, kStats, kCam, kNt>, kIsectBlock, lds) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, isect_queue_kernel<Tr, kStats, kNt>, kIsectBlock, lds) !=
             hipSuccess || per_cu <= 0)
         per_cu = 1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
@@ -2098,21 +1875,21 @@ static uint32_t persistent_blocks(size_t lds) {
     return cached;
 }
 
-template <typename Tr, bool kStats, bool kCam = false, bool kNt = false>
+template <typename Tr, bool kStats, bool kNt = false>
 static hipError_t launch_isect_queue_t(const IsectQueueArgs& a, uint32_t grid_items, hipStream_t s) {
     if (grid_items == 0) return hipSuccess;
     const size_t lds = (size_t)a.sc.stack_depth * Tr::kStackWords * kIsectBlock * sizeof(uint32_t) + Tr::kExtraLds;
-    const uint32_t full = persistent_blocks<Tr, kStats, kCam, kNt>(lds);
+    const uint32_t full = persistent_blocks<Tr, kStats, kNt>(lds);
     const uint32_t scaled = a.grid_q8 ? max(1u, (uint32_t)(((uint64_t)full * a.grid_q8) >> 8)) : full;
     const uint32_t blocks = min(scaled, blocks_for(grid_items, kIsectBlock));
-    hipLaunchKernelGGL((isect_queue_kernel<Tr, kStats, kCam, kNt>), dim3(blocks), dim3(kIsectBlock), lds, s, a);
+    hipLaunchKernelGGL((isect_queue_kernel<Tr, kStats, kNt>), dim3(blocks), dim3(kIsectBlock), lds, s, a);
     return hipGetLastError();
 }
 
 template <typename Tr, bool kNt>
 static uint32_t isect_queue_lanes_t(const IsectQueueArgs& a) {
     const size_t lds = (size_t)a.sc.stack_depth * Tr::kStackWords * kIsectBlock * sizeof(uint32_t) + Tr::kExtraLds;
-    const uint32_t full = persistent_blocks<Tr, false, false, kNt>(lds);
+    const uint32_t full = persistent_blocks<Tr, false, kNt>(lds);
     const uint32_t scaled = a.grid_q8 ? max(1u, (uint32_t)(((uint64_t)full * a.grid_q8) >> 8)) : full;
     return scaled * kIsectBlock;
 }
@@ -2125,20 +1902,13 @@ uint32_t isect_queue_lanes(const IsectQueueArgs& a) {
 
 hipError_t launch_isect_queue(const IsectQueueArgs& a, uint32_t grid_items, hipStream_t s) {
     if (!a.sc.nodes8)
-        return a.nt ? launch_isect_queue_t<Tracer, false, false, true>(a, grid_items, s)
+        return a.nt ? launch_isect_queue_t<Tracer, false, true>(a, grid_items, s)
                     : launch_isect_queue_t<Tracer, false>(a, grid_items, s);
     if (a.nt)
-        return a.sc.node6 ? launch_isect_queue_t<Tracer6, false, false, true>(a, grid_items, s)
-                          : launch_isect_queue_t<Tracer8, false, false, true>(a, grid_items, s);
+        return a.sc.node6 ? launch_isect_queue_t<Tracer6, false, true>(a, grid_items, s)
+                          : launch_isect_queue_t<Tracer8, false, true>(a, grid_items, s);
     return a.sc.node6 ? launch_isect_queue_t<Tracer6, false>(a, grid_items, s)
                       : launch_isect_queue_t<Tracer8, false>(a, grid_items, s);
-}
-
-// the isect launch that also starts the camera paths (IsectQueueArgs::cam)
-hipError_t launch_isect_queue_cam(const IsectQueueArgs& a, uint32_t grid_items, hipStream_t s) {
-    if (!a.sc.nodes8) return launch_isect_queue_t<Tracer, false, true>(a, grid_items, s);
-    return a.sc.node6 ? launch_isect_queue_t<Tracer6, false, true>(a, grid_items, s)
-                      : launch_isect_queue_t<Tracer8, false, true>(a, grid_items, s);
 }
 
 template <typename Tr, bool kNt>
@@ -2284,7 +2054,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     static thread_local uint32_t cached = 0;
     static thread_local int cached_dev = -1;
     // + the parked throughput / radiance of albedo / emitter lanes (render_fused_kernel)
-    const size_t park = kMode != kModeUnit && SPT_PARK_PATH ? (size_t)kIsectBlock * 32 : 0;
+    const size_t park = kMode != kModeUnit ? (size_t)kIsectBlock * 32 : 0;
     const size_t lds = (size_t)a.sc.stack_depth * Tr::kStackWords * kIsectBlock * sizeof(uint32_t) + Tr::kExtraLds + park;
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -2396,11 +2166,7 @@ hipError_t launch_fused(const FusedArgs& a, int mode, hipStream_t s, uint32_t* l
 }
 
 hipError_t launch_refill(const RefillArgs& a, uint32_t grid_items, hipStream_t s) {
-#if SPT_REFILL_STRIDE
     const dim3 g(std::min<uint32_t>(blocks_for(grid_items > 0 ? grid_items : 1, 256), kRefillMaxBlocks)), b(256);
-#else
-    const dim3 g(blocks_for(grid_items > 0 ? grid_items : 1, 256)), b(256);
-#endif
     if (a.nt) {
         if (a.mode == kModeEmit) hipLaunchKernelGGL((refill_kernel<kModeEmit, true>), g, b, 0, s, a);
         else if (a.mode == kModeAlbedo) hipLaunchKernelGGL((refill_kernel<kModeAlbedo, true>), g, b, 0, s, a);

@@ -313,12 +313,6 @@ struct IsectQueueArgs {
     uint32_t xcd_remap;              // 1: blocks sharing an XCD take adjacent static shares
     uint32_t drain_below;            // skip the launch when *count < drain_below (launch_drain takes the queue)
     unsigned long long* trav_stats;  // non-null: nodes, tris, lane steps, wave steps
-    // Camera paths started inside the launch (SPT_ISECT_CAMERA): the queue
-    // holds cam.surv survivors in slots [0, surv); the launch starts
-    // min(capacity - surv, work left) new camera paths in the slots after them
-    // (writing their rays for the shade) and does refill_kernel's bookkeeping
-    // in block 0's first thread (cam.isect_next: the NEXT launch's counter).
-    RefillArgs cam;
     uint32_t nt;                     // 1: non-temporal queue / hit accesses (spt_config.queue_cache)
 };
 
@@ -523,7 +517,6 @@ hipError_t launch_isect_queue(const IsectQueueArgs& a, uint32_t grid_items, hipS
 // one lane per queued ray, no lane refill: a fitting job's first cast (coherent camera rays)
 hipError_t launch_isect_lockstep(const IsectQueueArgs& a, uint32_t grid_items, hipStream_t s);
 hipError_t launch_isect_queue_stats(const IsectQueueArgs& a, uint32_t grid_items, hipStream_t s);
-hipError_t launch_isect_queue_cam(const IsectQueueArgs& a, uint32_t grid_items, hipStream_t s);
 hipError_t launch_isect_public(const IsectPublicArgs& a, hipStream_t s);
 hipError_t launch_fused(const FusedArgs& a, int mode, hipStream_t s, uint32_t* lanes_out);
 // The wavefront's drain: render_fused_kernel's lane loop over the paths of a

@@ -288,9 +288,6 @@ SPT_HD WoopShear woop_shear(const WoopRay& r, V3 p0, V3 p1, V3 p2) {
 // cull_tmin() (4e-6 below tmin) so a box the tree culls holds only triangles
 // this rule drops anyway.  For tmin > 0 the negative branch never decides
 // (E < 0 is below tmin either way), so the render's bits do not depend on it.
-#ifndef SPT_TRI_BOX_RULE
-#define SPT_TRI_BOX_RULE 1
-#endif
 constexpr float kCullTminRel = 4e-6f;
 SPT_HD float cull_tmin(float tmin) { return tmin - fabsf(tmin) * kCullTminRel; }
 constexpr float kBoxPadLo = 0.999999f;  // the pad for a negative exit (toward +inf)
@@ -360,9 +357,7 @@ SPT_HD bool woop_core(const WoopRay& r, const WoopShear& w, Reshear reshear, flo
     float T = (U * Az + V * Bz) + W * Cz;
     float t = T / det;
     if (!(t >= tmin && t <= tmax)) return false;
-#if SPT_TRI_BOX_RULE
     if (left_box_before_tmin(r, w, Az, Bz, Cz, tmin)) return false;
-#endif
     // + 0.0f: a zero t, u or v is +0.  Its sign would otherwise follow det's,
     // which the kx / ky order flips (the oracle keeps Woop's swap, the device
     // does not): with it every output bit is independent of that order.

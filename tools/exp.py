@@ -26,6 +26,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import re
 import shlex
 import subprocess
 import sys
@@ -59,7 +60,14 @@ def cmd_build(a):
     """make BUILD=build_<variant> EXTRA=<flags> for each variant the entry names."""
     e = manifest()[a.name]
     jobs = str(min(16, os.cpu_count() or 4))
+    csrc = os.path.join(PKG, "csrc")
+    sources = "".join(open(os.path.join(csrc, f), errors="replace").read() for f in sorted(os.listdir(csrc)))
     for var, extra in (e.get("build") or {}).items():
+        # a flag no source reads any more would build the default library under the variant's name
+        stale = [m for m in re.findall(r"-D(\w+)", extra) if not re.search(rf"\b{m}\b", sources)]
+        if stale:
+            sys.exit(f"{a.name}: build_{var} needs {', '.join('-D' + m for m in stale)}, which no file under csrc/ "
+                     "defines any more; check out the commit its EXPERIMENTS.md row names to rebuild it")
         print(f"== build_{var}: EXTRA={extra}", flush=True)
         subprocess.run(["make", "-s", "-j", jobs, "-C", PKG, f"BUILD=build_{var}", f"EXTRA={extra}", "ARCH=gfx950"],
                        check=True)
