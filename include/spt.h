@@ -409,6 +409,67 @@ spt_status spt_scene_set_material_kinds(spt_scene scene, const uint32_t* kinds, 
 spt_status spt_scene_set_texture(spt_scene scene, uint32_t material, const float* rgb, uint32_t width,
                                  uint32_t height);
 
+/* In-place geometry update: new vertex positions and normals for the scene's
+ * triangles, the acceleration structure refitted on the GPU instead of rebuilt
+ * (the update OptiX offers for its GAS; the reference never calls it).  For
+ * animation, simulation and interactive edits: an update costs a fraction of
+ * spt_scene_create_cfg and every material setter's state stays.
+ *
+ * After a successful call spt_intersect, spt_hit_info_compute, spt_render*
+ * and spt_render_aov give bit for bit the results of a scene created by
+ * spt_scene_create_cfg from these position and normal arrays with the
+ * original texcoords and material ids and the same albedo, emission, texture,
+ * sphere, kind and config calls applied: the closest hit does not depend on
+ * the tree, and a refitted tree's boxes still enclose their triangles.
+ *
+ * Unchanged: the topology (which triangles share a leaf, which nodes are
+ * siblings), the slot order, orig2slot, texcoords, material ids, the traversal
+ * stack depth and spt_scene_stats (sah_cost and build_ms stay "as built").
+ * The boxes grow as the mesh moves away from the one the tree was built for;
+ * spt_refit_stats.area_now / area_built says by how much (rebuild when the
+ * render rate no longer pays for the saved build).
+ *
+ * Arrays as for spt_scene_create: ntri must be the scene's triangle count;
+ * position indices in [0, nvert); nrm_tri NULL: every vertex normal is the
+ * geometric normal of the new triangle; a normal index of -1: the same for
+ * that vertex; else in [0, nnrm).  Positions and normals are always both
+ * rewritten (the scene does not keep nrm_tri).  spt_scene_update_geometry
+ * takes host arrays and checks the indices on the host;
+ * spt_scene_update_geometry_device takes device pointers, checks the indices
+ * with a kernel before anything is written, and runs its kernels on `stream`.
+ * A bad index, a count mismatch or a NULL required pointer returns
+ * SPT_ERR_INVALID and leaves the scene exactly as it was.  Non-finite
+ * positions do not fault (such triangles are never hit, as at creation).
+ *
+ * Like the other setters the call waits for the renders and public calls
+ * already queued (they see the geometry they were queued with), and it
+ * returns only after the device has finished the update.  A scene of 0
+ * triangles: the update succeeds and does nothing.  Works on loaded scenes
+ * (spt_scene_load), both builders, every bvh_width and pack_groups;
+ * spt_scene_save afterwards stores the updated scene. */
+typedef struct spt_refit_stats {
+    uint64_t updates;        /* completed updates of this scene (0: never updated) */
+    uint64_t nodes, tris;    /* wide (or BVH2) nodes refitted = spt_scene_stats.nodes; triangles rewritten */
+    uint32_t levels;         /* tree levels the plan holds */
+    uint32_t reserved;
+    uint64_t plan_bytes;     /* device memory the refit plan holds (0 until the first update) */
+    double plan_ms;          /* building the plan, once per scene */
+    double update_ms;        /* last update: host wall time of the call, quiesce included */
+    double refit_ms;         /* last update: GPU time of record rewrite + refit (HIP events) */
+    double area_built;       /* sum over nodes of the half surface area of the node's exact box, as built
+                                (for a loaded scene: as loaded) */
+    double area_now;         /* the same after the last update; area_now / area_built is the usual
+                                "rebuild when this grows" indicator */
+} spt_refit_stats;
+
+spt_status spt_scene_update_geometry(spt_scene scene, const int32_t* pos_tri, const float* pos, uint64_t nvert,
+                                     uint64_t ntri, const int32_t* nrm_tri, const float* nrm, uint64_t nnrm);
+spt_status spt_scene_update_geometry_device(spt_scene scene, const int32_t* pos_tri, const float* pos,
+                                            uint64_t nvert, uint64_t ntri, const int32_t* nrm_tri, const float* nrm,
+                                            uint64_t nnrm, void* stream);
+/* Zeros for a scene never updated. */
+spt_status spt_scene_get_refit_stats(spt_scene scene, spt_refit_stats* out);
+
 spt_status spt_scene_get_stats(spt_scene scene, spt_scene_stats* out);
 
 /* The host builders alone, without a device (diagnostics; the host sanitizer

@@ -22,6 +22,8 @@
 #include "host_error.h"
 #include "spt_internal.h"
 
+#include "bvh_refit.h"
+
 // Diagnostic build only (make BUILD=build_dbg EXTRA="-g -DSPT_SEGV_TRACE=1"):
 // a host segmentation fault prints the native backtrace (library offsets for
 // addr2line) before the default action.  Not in the product build.
@@ -352,6 +354,10 @@ struct spt_scene_t {
     spt_scene_stats stats{};
     Workspace ws;
     std::vector<PublicUse> pub;  // streams of public calls, with an event after the last one (quiesce)
+    // spt_scene_update_geometry: the plan is built by the first update
+    RefitPlan refit;
+    uint32_t* refit_bad = nullptr;  // the device validation's counter
+    spt_refit_stats refit_stats{};
 
     DeviceScene dev() const {
         DeviceScene d;
@@ -368,6 +374,8 @@ struct spt_scene_t {
         ws.release();
         hfree(nodes); hfree(nodes8); hfree(emission); hfree(tris); hfree(snrm); hfree(tc); hfree(orig2slot); hfree(albedo);
         hfree(tex_info); hfree(texels); hfree(spheres); hfree(sph_mat); hfree(mat_kind);
+        refit_plan_release(refit);
+        hfree(refit_bad);
     }
 };
 
@@ -1345,6 +1353,130 @@ spt_status spt_scene_set_material_kinds(spt_scene sc, const uint32_t* kinds, uin
     spt_status us = upload(&sc->mat_kind, kinds, sizeof(uint32_t) * nmat);
     if (us) return us;
     sc->nkind = nmat;
+    return SPT_OK;
+}
+
+namespace {
+
+// spt_scene_update_geometry[_device] once the arrays are on the device
+// (caller holds sc->mu and has made the scene's device current).
+spt_status update_geometry_locked(spt_scene_t* sc, const RefitMeshIn& m, bool validate, hipStream_t s, double t0) {
+    static const char* what = "spt_scene_update_geometry";
+    spt_status qs = quiesce_scene(sc);  // queued renders / calls see the geometry they were queued with
+    if (qs) return qs;
+    RefitScene rs{};
+    rs.nodes = sc->nodes8 ? sc->nodes8 : (uint4*)sc->nodes;
+    rs.fmt = sc->nodes8 ? (sc->node6 ? kRefitFmt6 : kRefitFmt8) : kRefitFmt2;
+    rs.group_shift = sc->group_shift;
+    rs.node_bytes = sc->node_bytes;
+    rs.tris = sc->tris;
+    rs.snrm = sc->snrm;
+    rs.orig2slot = sc->orig2slot;
+    rs.ntri = (uint32_t)sc->ntri;
+    if (validate) {  // before anything is written
+        if (!sc->refit_bad) HIP_TRY(hipMalloc((void**)&sc->refit_bad, sizeof(uint32_t)));
+        uint32_t bad = 0;
+        HIP_TRY(launch_refit_validate(rs, m, sc->refit_bad, s));
+        HIP_TRY(hipMemcpyAsync(&bad, sc->refit_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (bad)
+            return fail(SPT_ERR_INVALID, "%s: %u position / normal indices out of range [0,%llu) / [-1,%llu)", what,
+                        bad, (unsigned long long)m.nvert, (unsigned long long)m.nnrm);
+    }
+    if (!sc->refit.built) {
+        const char* why = nullptr;
+        const hipError_t e = refit_plan_build(rs, sc->stats.nodes, s, &sc->refit, &why);
+        if (why) return fail(SPT_ERR_HIP, "%s: refit plan: %s (%llu nodes expected)", what, why,
+                             (unsigned long long)sc->stats.nodes);
+        if (e) return fail(e == hipErrorOutOfMemory ? SPT_ERR_OOM : SPT_ERR_HIP, "%s: refit plan: %s", what,
+                           hipGetErrorString(e));
+    }
+    RefitPlan& p = sc->refit;
+    double area = 0.0;
+    float ms = 0.0f;
+    HIP_TRY(hipEventRecord(p.ev0, s));
+    HIP_TRY(launch_refit_update(rs, &m, p, true, s));
+    HIP_TRY(hipEventRecord(p.ev1, s));
+    HIP_TRY(hipMemcpyAsync(&area, p.area, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipEventElapsedTime(&ms, p.ev0, p.ev1));
+    spt_refit_stats& st = sc->refit_stats;
+    st.updates++;
+    st.nodes = p.nodes;
+    st.tris = sc->ntri;
+    st.levels = p.levels;
+    st.plan_bytes = p.bytes;
+    st.plan_ms = p.plan_ms;
+    st.refit_ms = ms;
+    st.area_built = p.area_built;
+    st.area_now = area;
+    st.update_ms = now_ms() - t0;
+    return SPT_OK;
+}
+
+spt_status update_geometry_args(spt_scene sc, const int32_t* pos_tri, const float* pos, uint64_t ntri,
+                                const int32_t* nrm_tri, const float* nrm, uint64_t nnrm) {
+    static const char* what = "spt_scene_update_geometry";
+    if (!sc) return fail(SPT_ERR_INVALID, "%s: NULL scene", what);
+    if (ntri != sc->ntri)
+        return fail(SPT_ERR_INVALID, "%s: %llu triangles given, the scene has %llu (the topology is fixed)", what,
+                    (unsigned long long)ntri, (unsigned long long)sc->ntri);
+    if (ntri > 0 && (!pos_tri || !pos)) return fail(SPT_ERR_INVALID, "%s: NULL positions", what);
+    if (nrm_tri && !nrm && nnrm) return fail(SPT_ERR_INVALID, "%s: normal indices without normals", what);
+    return SPT_OK;
+}
+
+}  // namespace
+
+spt_status spt_scene_update_geometry(spt_scene sc, const int32_t* pos_tri, const float* pos, uint64_t nvert,
+                                     uint64_t ntri, const int32_t* nrm_tri, const float* nrm, uint64_t nnrm) {
+    static const char* what = "spt_scene_update_geometry";
+    const double t0 = now_ms();
+    spt_status st = update_geometry_args(sc, pos_tri, pos, ntri, nrm_tri, nrm, nnrm);
+    if (st || ntri == 0) return st;
+    for (uint64_t t = 0; t < ntri; t++)
+        for (int k = 0; k < 3; k++) {
+            const int64_t pi = pos_tri[t * 3 + k];
+            if (pi < 0 || (uint64_t)pi >= nvert)
+                return fail(SPT_ERR_INVALID, "%s: triangle %llu position index %lld out of range [0,%llu)", what,
+                            (unsigned long long)t, (long long)pi, (unsigned long long)nvert);
+            const int64_t ni = nrm_tri ? nrm_tri[t * 3 + k] : -1;
+            if (ni < -1 || (ni >= 0 && (uint64_t)ni >= nnrm))
+                return fail(SPT_ERR_INVALID, "%s: triangle %llu normal index %lld out of range", what,
+                            (unsigned long long)t, (long long)ni);
+        }
+    DeviceGuard dg(sc->device);
+    struct Raw {
+        int32_t *pt = nullptr, *nt = nullptr;
+        float *p = nullptr, *n = nullptr;
+        ~Raw() { hfree(pt); hfree(nt); hfree(p); hfree(n); }
+    } raw;
+    if (!st) st = upload(&raw.pt, pos_tri, ntri * 3 * sizeof(int32_t));
+    if (!st) st = upload(&raw.p, pos, nvert * 3 * sizeof(float));
+    if (!st && nrm_tri) st = upload(&raw.nt, nrm_tri, ntri * 3 * sizeof(int32_t));
+    if (!st && nrm_tri) st = upload(&raw.n, nrm, nnrm * 3 * sizeof(float));
+    if (st) return st;
+    const RefitMeshIn m{raw.pt, raw.p, raw.nt, raw.n, nvert, nnrm};
+    std::lock_guard<std::mutex> lk(sc->mu);
+    return update_geometry_locked(sc, m, false, nullptr, t0);  // the null stream; the call is synchronous
+}
+
+spt_status spt_scene_update_geometry_device(spt_scene sc, const int32_t* pos_tri, const float* pos, uint64_t nvert,
+                                            uint64_t ntri, const int32_t* nrm_tri, const float* nrm, uint64_t nnrm,
+                                            void* stream) {
+    const double t0 = now_ms();
+    const spt_status st = update_geometry_args(sc, pos_tri, pos, ntri, nrm_tri, nrm, nnrm);
+    if (st || ntri == 0) return st;
+    DeviceGuard dg(sc->device);
+    const RefitMeshIn m{pos_tri, pos, nrm_tri, nrm, nvert, nnrm};
+    std::lock_guard<std::mutex> lk(sc->mu);
+    return update_geometry_locked(sc, m, true, (hipStream_t)stream, t0);
+}
+
+spt_status spt_scene_get_refit_stats(spt_scene sc, spt_refit_stats* out) {
+    if (!sc || !out) return fail(SPT_ERR_INVALID, "spt_scene_get_refit_stats: NULL argument");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    *out = sc->refit_stats;
     return SPT_OK;
 }
 

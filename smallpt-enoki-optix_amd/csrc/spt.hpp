@@ -91,6 +91,24 @@ class Scene {
     void render_aov(const spt_render_params& p, const spt_aov& planes, void* stream = nullptr) {
         check(spt_render_aov(scene_, &p, &planes, stream), "spt_render_aov");
     }
+    // spt_scene_update_geometry: new positions / normals for the committed
+    // triangles, the BVH refitted in place (host arrays; synchronous)
+    void update_geometry(const int32_t* pos_tri, const float* pos, uint64_t nvert, uint64_t ntri,
+                         const int32_t* nrm_tri = nullptr, const float* nrm = nullptr, uint64_t nnrm = 0) {
+        check(spt_scene_update_geometry(scene_, pos_tri, pos, nvert, ntri, nrm_tri, nrm, nnrm),
+              "spt_scene_update_geometry");
+    }
+    // ... device pointers, the kernels on `stream`
+    void update_geometry(const int32_t* pos_tri, const float* pos, uint64_t nvert, uint64_t ntri,
+                         const int32_t* nrm_tri, const float* nrm, uint64_t nnrm, void* stream) {
+        check(spt_scene_update_geometry_device(scene_, pos_tri, pos, nvert, ntri, nrm_tri, nrm, nnrm, stream),
+              "spt_scene_update_geometry_device");
+    }
+    spt_refit_stats refit_stats() const {
+        spt_refit_stats st{};
+        check(spt_scene_get_refit_stats(scene_, &st), "spt_scene_get_refit_stats");
+        return st;
+    }
     // Commit a mesh loaded elsewhere (read only: several devices' scenes may
     // be built from one host mesh, one thread per device).
     void commit_from(const Mesh& mesh, int device) {

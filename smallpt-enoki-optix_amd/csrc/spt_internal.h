@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "spt_math.h"
 
 namespace spt {
@@ -552,5 +554,58 @@ hipError_t launch_resolve_flags(const uint8_t* sflag, float* acc, float* out, ui
                                 uint32_t first_chunk, uint32_t last_chunk, uint32_t spp, float env_r, float env_g,
                                 float env_b, uint32_t order, unsigned long long* unwritten, hipStream_t s);
 hipError_t launch_hit_info(const HitInfoArgs& a, hipStream_t s);
+
+// ---- in-place geometry update (refit.hip, spt_scene_update_geometry)
+
+// The scene arrays an update rewrites, and the layout it has to know.
+struct RefitScene {
+    uint4* nodes;          // nodes8, or the BVH2 nodes (4 quads each)
+    int fmt;               // bvh_refit.h kRefitFmt8 / 6 / 2
+    uint32_t group_shift;
+    uint64_t node_bytes;   // bytes behind nodes
+    float4* tris;
+    float4* snrm;
+    const int32_t* orig2slot;
+    uint32_t ntri;
+};
+
+// New geometry on the device (spt_scene_update_geometry's arrays).
+struct RefitMeshIn {
+    const int32_t* pos_tri;  // 3 per triangle
+    const float* pos;        // 3 per vertex
+    const int32_t* nrm_tri;  // 3 per triangle or null (-1 = missing: geometric normal)
+    const float* nrm;
+    uint64_t nvert, nnrm;
+};
+
+// The refit plan of a scene: its reachable node slots grouped by level (root
+// first) and the per-slot scratch of exact boxes.  Built once, from one
+// download of the nodes; everything else stays on the device.
+struct RefitPlan {
+    uint32_t* order = nullptr;       // device: reachable node slots, level by level from the root
+    uint32_t* level_off = nullptr;   // device: levels + 1 offsets into order
+    float* boxes = nullptr;          // device: 6 floats (lo xyz, hi xyz) per node slot
+    double* area = nullptr;          // device: the pass's f64 sum of half areas
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<uint32_t> h_level_off;  // host copy of level_off (levels + 1 entries)
+    uint32_t levels = 0;
+    uint32_t top_levels = 0;         // levels [0, top_levels) refit in one single-block launch
+    uint64_t nodes = 0, bytes = 0;
+    double plan_ms = 0.0, area_built = 0.0;
+    bool built = false;
+};
+
+// why: set to a static message when the tree does not read as expected_nodes
+// reachable nodes (the caller fails rather than refit a tree it misread).
+hipError_t refit_plan_build(const RefitScene& sc, uint64_t expected_nodes, hipStream_t s, RefitPlan* plan,
+                            const char** why);
+void refit_plan_release(RefitPlan& plan);
+// Counts the out-of-range indices of m into *bad (zeroed first); writes nothing else.
+hipError_t launch_refit_validate(const RefitScene& sc, const RefitMeshIn& m, uint32_t* bad, hipStream_t s);
+// Pass 1 (triangle records and normals, skipped when m is null) and pass 2 (the
+// bottom-up refit; write = false only sums the areas of the boxes the current
+// records give).  *plan.area holds the sum of half areas afterwards.
+hipError_t launch_refit_update(const RefitScene& sc, const RefitMeshIn* m, const RefitPlan& plan, bool write,
+                               hipStream_t s);
 
 }  // namespace spt

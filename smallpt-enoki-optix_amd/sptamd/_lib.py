@@ -38,6 +38,7 @@ EXPORTED = [
     "spt_scene_isect_busy_begin", "spt_scene_isect_busy_end", "spt_scene_kernel_busy",
     "spt_debug_fail_workspace_alloc",
     "spt_render_aov", "spt_default_denoise_params", "spt_denoise_scratch_bytes", "spt_denoise",
+    "spt_scene_update_geometry", "spt_scene_update_geometry_device", "spt_scene_get_refit_stats",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -113,6 +114,17 @@ class SceneStats(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RefitStats(ctypes.Structure):
+    """spt_refit_stats: spt_scene_update_geometry's bookkeeping."""
+    _fields_ = [("updates", c_uint64), ("nodes", c_uint64), ("tris", c_uint64),
+                ("levels", c_uint32), ("reserved", c_uint32), ("plan_bytes", c_uint64),
+                ("plan_ms", c_double), ("update_ms", c_double), ("refit_ms", c_double),
+                ("area_built", c_double), ("area_now", c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
 class Config(ctypes.Structure):
@@ -215,6 +227,9 @@ def _load() -> ctypes.CDLL:
         "spt_default_denoise_params": (None, [POINTER(DenoiseParams)]),
         "spt_denoise_scratch_bytes": (ctypes.c_size_t, [u32, u32]),
         "spt_denoise": (i32, [POINTER(DenoiseParams), vp, POINTER(Aov), vp, vp, vp]),
+        "spt_scene_update_geometry": (i32, [vp, vp, vp, u64, u64, vp, vp, u64]),
+        "spt_scene_update_geometry_device": (i32, [vp, vp, vp, u64, u64, vp, vp, u64, vp]),
+        "spt_scene_get_refit_stats": (i32, [vp, POINTER(RefitStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -342,7 +357,7 @@ def tile_rows(height: int, tile_index: int, tile_count: int, rows_per_group: int
 
 __all__ = [
     "lib", "check", "SptError", "Rays", "Hits", "HitInfo", "Camera", "RenderParams", "RenderStats",
-    "SceneStats", "Mesh", "Config", "Aov", "AOV_PLANES", "DenoiseParams", "default_denoise_params", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
+    "SceneStats", "RefitStats", "Mesh", "Config", "Aov", "AOV_PLANES", "DenoiseParams", "default_denoise_params", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
     "LIB_PATH", "REPO_ROOT",
     "PCG32_DEFAULT_STATE", "SPT_RNG_Y_FIRST", "SPT_RNG_X_FIRST", "SPT_FLAG_TIMING", "c_uint8",
 ]

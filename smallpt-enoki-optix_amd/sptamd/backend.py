@@ -227,6 +227,45 @@ class HipBackend:
         check(lib.spt_scene_set_texture(self._scene, material, img.ctypes.data, img.shape[1], img.shape[0]),
               "spt_scene_set_texture")
 
+    def update_geometry(self, position_triplets, positions, shading_normal_triplets=None, shading_normals=None,
+                        stream=None) -> None:
+        """spt_scene_update_geometry: new positions / normals for the scene's
+        triangles, the BVH refitted in place (no rebuild; every material setter's
+        state stays).  Numpy arrays take the host call; if `positions` is a CUDA
+        tensor every given array must be one (int32 / float32) and the device
+        call runs on `stream` (default: torch's current stream).  Synchronous."""
+        if isinstance(positions, torch.Tensor) and positions.is_cuda:
+            given = [a for a in (position_triplets, shading_normal_triplets, shading_normals) if a is not None]
+            if not all(isinstance(a, torch.Tensor) and a.is_cuda for a in given):
+                raise TypeError("update_geometry: with CUDA positions every given array must be a CUDA tensor")
+            pt = position_triplets.to(torch.int32).contiguous().reshape(-1)
+            pos = positions.to(torch.float32).contiguous().reshape(-1)
+            nt = None if shading_normal_triplets is None else shading_normal_triplets.to(torch.int32).contiguous().reshape(-1)
+            nrm = None if shading_normals is None else shading_normals.to(torch.float32).contiguous().reshape(-1)
+            # (conversions above ran on torch's current stream)
+            s = stream if stream is not None else torch.cuda.current_stream(pos.device)
+            s.wait_stream(torch.cuda.current_stream(pos.device))
+            check(lib.spt_scene_update_geometry_device(
+                self._scene, pt.data_ptr(), pos.data_ptr(), pos.numel() // 3, pt.numel() // 3,
+                None if nt is None else nt.data_ptr(), None if nrm is None else nrm.data_ptr(),
+                0 if nrm is None else nrm.numel() // 3, s.cuda_stream or None), "spt_scene_update_geometry_device")
+            return
+        pt = np.ascontiguousarray(np.asarray(position_triplets, dtype=np.int32).reshape(-1))
+        pos = None if positions is None else np.ascontiguousarray(np.asarray(positions, dtype=np.float32).reshape(-1))
+        nt = None if shading_normal_triplets is None else np.ascontiguousarray(
+            np.asarray(shading_normal_triplets, dtype=np.int32).reshape(-1))
+        nrm = None if shading_normals is None else np.ascontiguousarray(
+            np.asarray(shading_normals, dtype=np.float32).reshape(-1))
+        check(lib.spt_scene_update_geometry(
+            self._scene, _host_ptr(pt), _host_ptr(pos), 0 if pos is None else pos.size // 3, pt.size // 3,
+            _host_ptr(nt), _host_ptr(nrm), 0 if nrm is None else nrm.size // 3), "spt_scene_update_geometry")
+
+    def refit_stats(self) -> dict:
+        """spt_scene_get_refit_stats as a dict (zeros before the first update)."""
+        st = _lib.RefitStats()
+        check(lib.spt_scene_get_refit_stats(self._scene, ctypes.byref(st)), "spt_scene_get_refit_stats")
+        return st.as_dict()
+
     def save(self, path: str, extra: bytes = b"") -> None:
         """spt_scene_save: the committed scene (BVH, arrays, materials) + extra bytes to one file."""
         check(lib.spt_scene_save(self._scene, os.fsencode(path), extra or None, len(extra)), "spt_scene_save")
@@ -413,6 +452,41 @@ class Scene:
             self.backend.set_spheres(m["spheres"], m.get("sphere_mat"))
         if m.get("kinds") is not None:
             self.backend.set_material_kinds(m["kinds"])
+
+    def update_geometry(self, pos, nrm=None, pos_tri=None, nrm_tri=None, stream=None) -> None:
+        """HipBackend.update_geometry with the triplets of self.mesh unless
+        given: pos (and nrm, if nrm_tri is given or the mesh has one) replace the
+        mesh's arrays.  With numpy inputs self.mesh becomes a shallow copy that
+        carries the new arrays.  A cache-loaded scene (mesh None) needs pos_tri."""
+        m = self.mesh
+        if pos_tri is None:
+            if m is None:
+                raise ValueError("update_geometry: a loaded scene has no mesh; pass pos_tri")
+            pos_tri = m["pos_tri"]
+        if nrm_tri is None and nrm is not None and m is not None:
+            nrm_tri = m.get("nrm_tri")
+        if nrm_tri is None:
+            nrm = None
+        elif nrm is None:
+            raise ValueError("update_geometry: nrm_tri without nrm")
+        on_dev = isinstance(pos, torch.Tensor) and pos.is_cuda
+        if on_dev:
+            dev = pos.device
+            pos_tri = torch.as_tensor(np.asarray(pos_tri, dtype=np.int32), device=dev) \
+                if not isinstance(pos_tri, torch.Tensor) else pos_tri
+            if nrm_tri is not None and not isinstance(nrm_tri, torch.Tensor):
+                nrm_tri = torch.as_tensor(np.asarray(nrm_tri, dtype=np.int32), device=dev)
+        self.backend.update_geometry(pos_tri, pos, nrm_tri, nrm, stream=stream)
+        if m is not None and not on_dev:
+            m = dict(m)
+            m["pos"] = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
+            m["pos_tri"] = pos_tri
+            if nrm_tri is not None:
+                m["nrm"], m["nrm_tri"] = np.asarray(nrm, dtype=np.float32).reshape(-1, 3), nrm_tri
+            else:
+                m.pop("nrm", None)
+                m.pop("nrm_tri", None)
+            self.mesh = m
 
     def save(self, path: str) -> None:
         """Binary scene cache of the committed scene (spt_scene_save); pbrt_info rides
