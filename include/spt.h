@@ -577,6 +577,56 @@ spt_status spt_render_async(spt_scene scene, const spt_render_params* params, fl
                             uint64_t* ticket);
 spt_status spt_render_wait(spt_scene scene, uint64_t ticket, spt_render_stats* stats);
 
+/* Progressive rendering (a build addition: the reference renders its spp in one
+ * go, main.cpp:385-429): one pass adds samples [sample_base, sample_base + spp)
+ * of every tile pixel onto running sums the caller owns, so an image can be
+ * shown early and refined, continued later, and stopped when its variance is
+ * low enough.
+ *
+ * Samples.  Sample s of a pixel is the sample spt_render traces as its sample s
+ * in a render of any spp > s with the same other parameters (a sample's random
+ * numbers do not depend on spp).  max_depth, rng_initstate, rng_order, the
+ * camera and the tile must be the same in every pass of one accumulation;
+ * keeping them and the scene's state the same is the caller's part.
+ * Sums.  With x_s the sample's contribution as spt_render adds it (unit mode:
+ * env[c] or 0), sum becomes (((sum + x_b) + x_{b+1}) + ...) in f32, in sample
+ * order, and sum_sq the same with x_s * x_s, the product rounded to f32 before
+ * the add.
+ * Film.  film = sum / (float)n, n = sample_base + spp.
+ * Variance (of the pixel mean, per channel).  m = sum / (float)n,
+ * q = sum_sq / (float)n, variance = n < 2 ? 0 : fmaxf(q - m * m, 0) / (float)(n - 1),
+ * each operation rounded to f32.
+ * So, bit for bit: any split of [0, N) into consecutive passes gives the sum,
+ * sum_sq, film and variance of one pass of N; that film is spt_render's at
+ * spp = N; and the pipeline, work order, streams, film chunking inside a pass
+ * and lockstep_first never change them.
+ * Errors, all before any device work: SPT_ERR_INVALID for a NULL acc or sum,
+ * variance without sum_sq, reserved != 0, or two of the four buffers
+ * overlapping; SPT_ERR_LIMIT for sample_base + spp >= 2^24 (n exact in f32);
+ * otherwise spt_render's validation.  The buffers are untouched after an error.
+ * Stats describe the pass: paths = tile pixels x params->spp.
+ * Threading and ordering as for spt_render / spt_render_async; the ticket of
+ * spt_render_accum_async is collected by spt_render_wait and counts toward its
+ * limit of 64.  Passes of one accumulation are queued on one caller stream:
+ * stream order makes pass k + 1 read what pass k wrote, with no
+ * synchronisation by the caller in between.  The call writes nothing outside
+ * the planes it was given, and reads sum / sum_sq only when sample_base > 0. */
+typedef struct spt_accum {
+    uint32_t sample_base;  /* samples already in sum: this call renders samples
+                              [sample_base, sample_base + params->spp) of every tile pixel */
+    uint32_t reserved;     /* 0 */
+    float* sum;            /* in/out, 3 x tile_rows x width, required: running f32 sum per channel.
+                              Read only when sample_base > 0 (sample_base == 0 starts from 0
+                              whatever the buffer holds) */
+    float* sum_sq;         /* in/out, same shape, may be NULL: running f32 sum of x*x per channel */
+    float* film;           /* out, may be NULL: sum / (float)(sample_base + spp) */
+    float* variance;       /* out, may be NULL, needs sum_sq: variance of the pixel mean, per channel */
+} spt_accum;
+spt_status spt_render_accum(spt_scene scene, const spt_render_params* params, const spt_accum* acc,
+                            spt_render_stats* stats, void* stream);
+spt_status spt_render_accum_async(spt_scene scene, const spt_render_params* params, const spt_accum* acc,
+                                  void* stream, uint64_t* ticket);
+
 /* First-hit feature buffers (AOVs) of a tile, lined up with spt_render's
  * samples (a build addition: the reference saves one radiance film,
  * main.cpp:431-433).  Planar, tile_rows x width floats per plane, tile rows in
@@ -663,6 +713,53 @@ size_t spt_denoise_scratch_bytes(uint32_t width, uint32_t height);
  * pixels or more.  These checks need no device. */
 spt_status spt_denoise(const spt_denoise_params* p, const float* color, const spt_aov* guides, float* out,
                        void* scratch, void* stream);
+
+/* Variance-guided a-trous filter: spt_denoise with the colour term measured in
+ * estimated standard deviations of the pixel itself and the variance filtered
+ * along with the colour — the spatial filter of Schied et al. 2017
+ * ("Spatiotemporal Variance-Guided Filtering") (a build addition).  No
+ * radiance-unit sigma to rescale with the scene's brightness: the variance
+ * planes of spt_render_accum carry the scale.
+ *   v_0(p) = fmaxf((var_r + var_g) + var_b, 0).
+ * Iteration i = 0 .. iterations-1 has step 2^i:
+ *   vt(p) = sum g v_i(q) / sum g over the 3 x 3 taps q = p + (dx, dy), dx, dy in
+ *           [-1, 1], inside the image (adjacent pixels at every iteration, not
+ *           dilated), g = g1[|dx|] g1[|dy|], g1 = {1/2, 1/4};
+ *   e_c = |c_i(p) - c_i(q)|^2 / (sigma_variance^2 vt(p) + 1e-10);
+ *   e_n, e_a, e_z, the 5 x 5 taps q = p + 2^i (dx, dy) and k exactly spt_denoise's;
+ *   w = k expf(-(e_c + e_n + e_a + e_z));
+ *   c_{i+1}(p) = sum w c_i(q) / sum w;     v_{i+1}(p) = sum w^2 v_i(q) / (sum w)^2.
+ * sigma_variance <= 0 switches the colour term off (the variance is still
+ * propagated); the other sigmas and NULL guides as for spt_denoise.  A pixel of
+ * variance 0 (converged, e.g. the sky) only mixes with pixels of its own
+ * colour.  variance_out is the filtered image's remaining variance estimate
+ * (max v_out <= max v_0). */
+typedef struct spt_denoise_var_params {
+    uint32_t width, height;
+    uint32_t iterations;        /* 0..8; 0 copies color to out and v_0 to variance_out */
+    float sigma_variance, sigma_normal, sigma_albedo, sigma_depth;
+} spt_denoise_var_params;
+
+/* width = height = 0 (set them), 5 iterations, sigma_variance 4 (the paper's
+ * value, in standard deviations: independent of the radiance scale), the other
+ * sigmas as spt_default_denoise_params. */
+void spt_default_denoise_var_params(spt_denoise_var_params* p);
+
+/* Bytes of device scratch spt_denoise_var needs: two images of 3 colour planes
+ * and 1 variance plane (2 x (3 + 1) x 4 x width x height). */
+size_t spt_denoise_var_scratch_bytes(uint32_t width, uint32_t height);
+
+/* color, variance, out: 3 planes of width x height floats on the device
+ * (spt_render_accum's film and variance); variance_out: 1 plane, may be NULL.
+ * out and variance_out MUST NOT alias color, variance, scratch or each other.
+ * scratch: spt_denoise_var_scratch_bytes device bytes (may be NULL only when
+ * iterations = 0).  Whole images only; the call has no scene, never allocates,
+ * and queues 1 + `iterations` launches on `stream`.  SPT_ERR_INVALID: NULL
+ * params, a zero size, iterations > 8, NULL color, variance or out, out == color,
+ * NULL scratch with iterations > 0; SPT_ERR_LIMIT: 2^31 pixels or more.  These
+ * checks need no device. */
+spt_status spt_denoise_var(const spt_denoise_var_params* p, const float* color, const float* variance,
+                           const spt_aov* guides, float* out, float* variance_out, void* scratch, void* stream);
 
 /* The isect kernel's busy time across queued renders (a build addition, for the
  * roofline: renders queued back to back overlap, so per-render busy times do

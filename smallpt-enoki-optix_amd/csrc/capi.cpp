@@ -220,22 +220,29 @@ struct PublicUse {
     hipEvent_t ev;
 };
 
-// The PCG32 jump table of one (spp, depth, seed) key: [spp] seeded sample maps,
-// then [depth] cast jumps (read-only while renders run).  A workspace keeps a
-// few, so a caller that changes the seed per render (progressive accumulation)
-// reuses them; a table is rewritten (on the render's stream, from its own
-// pinned staging copy) only after every render that read it has finished —
-// ev[s] is recorded after each render of working set s that used the table,
-// and a set's renders run in order — and a render on another stream waits
-// for the write (write_ev).  No device-wide synchronisation.
+// The PCG32 jump table of one (depth, seed) key: [kMaxDepthCasts] cast jumps,
+// then the seeded sample maps of samples [0, n) (read-only while renders run).
+// A sample's entry does not depend on the render's spp, so one table serves
+// every render and every spt_render_accum pass of its key whose samples end at
+// or below n; more samples append a tail (on the render's stream, from the
+// table's pinned staging copy) without touching what queued renders read, and
+// the table grows geometrically.  A workspace keeps a few, so a caller that
+// changes the seed per render reuses them; a table is re-keyed or reallocated
+// only after every render that read it has finished — ev[s] is recorded after
+// each render of working set s that used the table, and a set's renders run in
+// order — and a render on another stream waits for the writes (write_ev; each
+// write follows the one before, so the last event covers them all).  No
+// device-wide synchronisation.
 constexpr int kJumpTables = 4;
 struct JumpTable {
     PcgJump* dev = nullptr;
     PcgJump* host = nullptr;            // pinned staging of the last write
-    size_t cap = 0;
-    uint32_t spp = 0, depth = 0;
+    size_t cap = 0;                     // sample entries the buffers hold (after the cast jumps)
+    uint32_t n = 0, depth = 0;          // sample entries written
     uint64_t state = 0;
     bool valid = false;
+    const PcgJump* casts() const { return dev; }
+    const PcgJump* samples() const { return dev + kMaxDepthCasts; }
     uint64_t lru = 0;
     hipEvent_t write_ev = nullptr;
     hipEvent_t ev[kWorkSets] = {};
@@ -601,53 +608,77 @@ spt_status release_queues(WorkSet& ws) {
     return SPT_OK;
 }
 
-// The PCG32 jump table of a render (JumpTable): to each sample's first draw,
-// s * (4 + 2D), and from there to the bounce draw of each cast, 4 + 2 * cast
-// (main.cpp:395,396,413).  [spp] per sample: seed(initstate, .) then the jump
-// past s * (4 + 2D) draws, as one affine map of the stream constant
-// (spt_math.h pcg_seeded_jump); then [depth] per cast: the jump past 4 + 2 cast
-// draws.  A hit costs nothing; a miss rewrites the least recently used table
-// on `stream` once the renders that read it are done.
-spt_status ensure_jumps(Workspace& w, hipStream_t stream, uint32_t spp, uint32_t depth, uint64_t initstate,
+// The PCG32 jump table of a render (JumpTable): from each cast's first draw to
+// its bounce draw, 4 + 2 * cast (main.cpp:395,396,413), and to each sample's
+// first draw, s * (4 + 2D): seed(initstate, .) then the jump past s * (4 + 2D)
+// draws, as one affine map of the stream constant (spt_math.h
+// pcg_seeded_jump).  `nsamples`: the table must hold samples [0, nsamples).  A
+// hit costs nothing; more samples of a known key write the new tail only; a
+// new key rewrites the least recently used table once the renders that read it
+// are done, and so does a table outgrown (then at least doubled).
+spt_status ensure_jumps(Workspace& w, hipStream_t stream, uint32_t nsamples, uint32_t depth, uint64_t initstate,
                         JumpTable** out) {
     JumpTable* t = nullptr;
     for (JumpTable& x : w.jt)
-        if (x.valid && x.spp == spp && x.depth == depth && x.state == initstate) t = &x;
-    if (t) {
+        if (x.valid && x.depth == depth && x.state == initstate) t = &x;
+    const uint64_t per_sample = 4ull + 2ull * depth;
+    if (t && nsamples <= t->cap) {
         t->lru = ++w.jt_clock;
         HIP_TRY(hipStreamWaitEvent(stream, t->write_ev, 0));  // written on another stream, perhaps
+        if (nsamples > t->n) {
+            // the tail: entries nobody reads yet, staged where no copy is in flight
+            PcgJump* h = t->host + kMaxDepthCasts;
+            for (uint32_t s = t->n; s < nsamples; s++)
+                h[s] = pcg_seeded_jump(initstate, pcg_jump_coeffs((uint64_t)s * per_sample));
+            HIP_TRY(hipMemcpyAsync(t->dev + kMaxDepthCasts + t->n, h + t->n, sizeof(PcgJump) * (nsamples - t->n),
+                                   hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipEventRecord(t->write_ev, stream));
+            t->n = nsamples;
+        }
         *out = t;
         return SPT_OK;
     }
-    t = &w.jt[0];
-    for (JumpTable& x : w.jt)
-        if (!x.valid ? t->valid : x.lru < t->lru) t = &x;
+    const bool grow = t != nullptr;  // the key's table, outgrown: its entries stay valid
+    if (!t) {
+        t = &w.jt[0];
+        for (JumpTable& x : w.jt)
+            if (!x.valid ? t->valid : x.lru < t->lru) t = &x;
+    }
     for (int k = 0; k < kWorkSets; k++)
         if (t->ev_used[k]) HIP_TRY(hipEventSynchronize(t->ev[k]));  // the renders that read it
     if (t->aov_used) HIP_TRY(hipEventSynchronize(t->aov_ev));       // and the spt_render_aov calls
     t->aov_used = false;
     if (t->write_ev) HIP_TRY(hipEventSynchronize(t->write_ev));     // and its last write (staging reuse)
     t->valid = false;
-    const size_t n = (size_t)spp + kMaxDepthCasts;
-    if (n > t->cap) {
+    uint32_t have = grow ? t->n : 0;
+    if (nsamples > t->cap) {
+        const size_t cap = std::max<size_t>(std::max<size_t>(nsamples, 2 * t->cap), 64);
+        PcgJump* dev = nullptr;
+        PcgJump* host = nullptr;
+        HIP_TRY(hipMalloc((void**)&dev, sizeof(PcgJump) * (cap + kMaxDepthCasts)));
+        if (hipHostMalloc((void**)&host, sizeof(PcgJump) * (cap + kMaxDepthCasts), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            hfree(dev);
+            return fail(SPT_ERR_OOM, "spt_render: no pinned memory for the jump table");
+        }
+        if (have) memcpy(host + kMaxDepthCasts, t->host + kMaxDepthCasts, sizeof(PcgJump) * have);
         hfree(t->dev);
         if (t->host) (void)hipHostFree(t->host);
-        t->host = nullptr;
-        t->cap = 0;
-        HIP_TRY(hipMalloc((void**)&t->dev, sizeof(PcgJump) * n));
-        HIP_TRY(hipHostMalloc((void**)&t->host, sizeof(PcgJump) * n, hipHostMallocDefault));
-        t->cap = n;
+        t->dev = dev;
+        t->host = host;
+        t->cap = cap;
     }
     if (!t->write_ev) HIP_TRY(hipEventCreateWithFlags(&t->write_ev, hipEventDisableTiming));
     for (auto& e : t->ev)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const uint64_t per_sample = 4ull + 2ull * depth;
-    for (uint32_t s = 0; s < spp; s++) t->host[s] = pcg_seeded_jump(initstate, pcg_jump_coeffs((uint64_t)s * per_sample));
-    for (uint32_t j = 0; j < depth; j++) t->host[(size_t)spp + j] = pcg_jump_coeffs(4ull + 2ull * j);
-    HIP_TRY(hipMemcpyAsync(t->dev, t->host, sizeof(PcgJump) * ((size_t)spp + depth), hipMemcpyHostToDevice, stream));
+    for (uint32_t j = 0; j < kMaxDepthCasts; j++) t->host[j] = pcg_jump_coeffs(4ull + 2ull * j);
+    PcgJump* h = t->host + kMaxDepthCasts;
+    for (uint32_t s = have; s < nsamples; s++) h[s] = pcg_seeded_jump(initstate, pcg_jump_coeffs((uint64_t)s * per_sample));
+    HIP_TRY(hipMemcpyAsync(t->dev, t->host, sizeof(PcgJump) * ((size_t)kMaxDepthCasts + nsamples), hipMemcpyHostToDevice,
+                           stream));
     HIP_TRY(hipEventRecord(t->write_ev, stream));
     for (bool& u : t->ev_used) u = false;
-    t->spp = spp;
+    t->n = nsamples;
     t->depth = depth;
     t->state = initstate;
     t->valid = true;
@@ -2115,7 +2146,7 @@ spt_status spt_render_aov(spt_scene sc, const spt_render_params* pp, const spt_a
     JumpTable* jtab = nullptr;
     spt_status st = ensure_jumps(sc->ws, stream, p.spp, p.max_depth, p.rng_initstate, &jtab);
     if (st) return st;
-    a.sample_jump = jtab->dev;
+    a.sample_jump = jtab->samples();
     if (!jtab->aov_ev) HIP_TRY(hipEventCreateWithFlags(&jtab->aov_ev, hipEventDisableTiming));
     if (jtab->aov_used && jtab->aov_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, jtab->aov_ev, 0));
     HIP_TRY(launch_aov(a, stream));
@@ -2185,10 +2216,101 @@ spt_status spt_denoise(const spt_denoise_params* pp, const float* color, const s
     return SPT_OK;
 }
 
-spt_status spt_render_async(spt_scene sc, const spt_render_params* pp, float* film_dev, void* caller_,
-                            uint64_t* ticket_out) {
+void spt_default_denoise_var_params(spt_denoise_var_params* p) {
+    if (!p) return;
+    p->width = p->height = 0;
+    p->iterations = 5;
+    p->sigma_variance = 4.0f;
+    p->sigma_normal = 0.5f;
+    p->sigma_albedo = 0.2f;
+    p->sigma_depth = 0.1f;
+}
+
+size_t spt_denoise_var_scratch_bytes(uint32_t width, uint32_t height) {
+    return (size_t)2 * (3 + 1) * sizeof(float) * (size_t)width * (size_t)height;
+}
+
+spt_status spt_denoise_var(const spt_denoise_var_params* pp, const float* color, const float* variance,
+                           const spt_aov* guides, float* out, float* variance_out, void* scratch, void* stream_) {
+    if (!pp) return fail(SPT_ERR_INVALID, "spt_denoise_var: NULL params");
+    const spt_denoise_var_params& p = *pp;
+    if (p.width == 0 || p.height == 0) return fail(SPT_ERR_INVALID, "spt_denoise_var: width/height must be > 0");
+    if (p.iterations > 8) return fail(SPT_ERR_INVALID, "spt_denoise_var: iterations %u > 8", p.iterations);
+    if (!color || !out || !variance) return fail(SPT_ERR_INVALID, "spt_denoise_var: NULL color / variance / out");
+    if (color == out) return fail(SPT_ERR_INVALID, "spt_denoise_var: out must not alias color");
+    if (variance == out || (variance_out && (variance_out == out || variance_out == color || variance_out == variance)))
+        return fail(SPT_ERR_INVALID, "spt_denoise_var: out / variance_out must not alias an input or each other");
+    if (p.iterations > 0 && !scratch) return fail(SPT_ERR_INVALID, "spt_denoise_var: NULL scratch");
+    if ((uint64_t)p.width * p.height >= (1ull << 31)) return fail(SPT_ERR_LIMIT, "spt_denoise_var: image too large");
+    const hipStream_t stream = (hipStream_t)stream_;
+    const size_t P = (size_t)p.width * p.height;
+    if (p.iterations == 0) {
+        HIP_TRY(hipMemcpyAsync(out, color, 3 * P * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (variance_out) HIP_TRY(launch_denoise_var_init(variance, variance_out, (uint32_t)P, stream));
+        return SPT_OK;
+    }
+    DenoiseVarArgs a{};
+    a.width = p.width;
+    a.height = p.height;
+    const auto inv_sq = [](float sigma) { return sigma > 0.0f ? std::min(1.0f / (sigma * sigma), 3.0e38f) : 0.0f; };
+    a.sv2 = p.sigma_variance > 0.0f ? std::min(p.sigma_variance * p.sigma_variance, 3.0e38f) : 0.0f;
+    if (guides && guides->normal_x && guides->normal_y && guides->normal_z) {
+        a.normal_x = guides->normal_x; a.normal_y = guides->normal_y; a.normal_z = guides->normal_z;
+        a.inv_normal = inv_sq(p.sigma_normal);
+    }
+    if (guides && guides->albedo_r && guides->albedo_g && guides->albedo_b) {
+        a.albedo_r = guides->albedo_r; a.albedo_g = guides->albedo_g; a.albedo_b = guides->albedo_b;
+        a.inv_albedo = inv_sq(p.sigma_albedo);
+    }
+    if (guides && guides->depth) {
+        a.depth = guides->depth;
+        a.inv_depth = inv_sq(p.sigma_depth);
+    }
+    // two images of 3 colour planes + 1 variance plane; v_0 starts in the second
+    // image's variance plane, which iteration 1 is the first to overwrite
+    float* const ping[2] = {(float*)scratch, (float*)scratch + 4 * P};
+    HIP_TRY(launch_denoise_var_init(variance, ping[1] + 3 * P, (uint32_t)P, stream));
+    const float* src = color;
+    const float* vsrc = ping[1] + 3 * P;
+    for (uint32_t i = 0; i < p.iterations; i++) {
+        const bool last = i + 1 == p.iterations;
+        a.src = src;
+        a.vsrc = vsrc;
+        a.dst = last ? out : ping[i & 1u];
+        a.vdst = last ? variance_out : ping[i & 1u] + 3 * P;
+        a.step = 1u << i;
+        HIP_TRY(launch_denoise_var(a, stream));
+        src = a.dst;
+        vsrc = a.vdst;
+    }
+    return SPT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Byte ranges [a, a + n) and [b, b + n) overlap (either may be null: no range).
+bool ranges_overlap(const void* a, const void* b, uint64_t n) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y ? y - x < n : x - y < n;
+}
+
+// spt_render_async (accum null: the film is sum / spp, the running sum in the
+// working set) and spt_render_accum_async (accum: samples [sample_base,
+// sample_base + spp) added onto the caller's sums) — one render loop; the two
+// differ in where the jump table is read and in the resolve.
+spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film_dev, const spt_accum* accum,
+                          bool accum_call, void* caller_, uint64_t* ticket_out) {
     const double wall0 = now_ms();
     if (!sc || !pp || !ticket_out) return fail(SPT_ERR_INVALID, "spt_render: NULL argument");
+    if (accum_call) {
+        if (!accum || !accum->sum) return fail(SPT_ERR_INVALID, "spt_render_accum: NULL accumulator / sum");
+        if (accum->reserved != 0) return fail(SPT_ERR_INVALID, "spt_render_accum: reserved must be 0");
+        if (accum->variance && !accum->sum_sq)
+            return fail(SPT_ERR_INVALID, "spt_render_accum: variance needs sum_sq");
+    }
     const spt_render_params& p = *pp;
     if (p.width == 0 || p.height == 0 || p.spp == 0 || p.max_depth == 0)
         return fail(SPT_ERR_INVALID, "spt_render: width/height/spp/max_depth must be > 0");
@@ -2205,7 +2327,18 @@ spt_status spt_render_async(spt_scene sc, const spt_render_params* pp, float* fi
     const hipStream_t caller = (hipStream_t)caller_;
     const uint32_t rows = spt_tile_rows(p.height, p.tile_index, p.tile_count, p.rows_per_group, nullptr, 0);
     const uint64_t P = (uint64_t)rows * p.width;
-    if (P != 0 && !film_dev) return fail(SPT_ERR_INVALID, "spt_render: NULL film");
+    if (P != 0 && !film_dev && !accum) return fail(SPT_ERR_INVALID, "spt_render: NULL film");
+    const uint32_t sample_base = accum ? accum->sample_base : 0u;
+    if (accum) {
+        // n = sample_base + spp stays exact in f32
+        if ((uint64_t)sample_base + p.spp >= (1ull << 24))
+            return fail(SPT_ERR_LIMIT, "spt_render_accum: sample_base + spp must be < 2^24");
+        const void* planes[4] = {accum->sum, accum->sum_sq, accum->film, accum->variance};
+        for (int i = 0; i < 4; i++)
+            for (int j = i + 1; j < 4; j++)
+                if (planes[i] && (planes[i] == planes[j] || ranges_overlap(planes[i], planes[j], 12ull * P)))
+                    return fail(SPT_ERR_INVALID, "spt_render_accum: sum, sum_sq, film and variance must not overlap");
+    }
     DeviceGuard dg(sc->device);
     std::lock_guard<std::mutex> lock(sc->mu);  // the scene's one workspace
     RenderSlot* slot = nullptr;
@@ -2409,8 +2542,14 @@ retry_fit:
     HIP_TRY(hipEventRecord(ws.call_ev, caller));
     HIP_TRY(hipStreamWaitEvent(stream, ws.call_ev, 0));
     JumpTable* jtab = nullptr;
-    if ((st = ensure_jumps(sc->ws, stream, p.spp, p.max_depth, p.rng_initstate, &jtab))) return st;
-    const PcgJump* jumps = jtab->dev;
+    if ((st = ensure_jumps(sc->ws, stream, sample_base + p.spp, p.max_depth, p.rng_initstate, &jtab))) return st;
+    // A pass runs as the sample chunks [sample_base, sample_base + spp) of a longer
+    // render: the kernels take a chunk's first sample (sample0 / chunk_s0), index
+    // the table by the absolute sample and key the roulette's hash by it
+    // (rr_uniform), so sample s of a pass is sample s of any render
+    const PcgJump* jumps = jtab->samples();
+    const PcgJump* cjumps = jtab->casts();
+    const uint32_t s_begin = sample_base, s_end = sample_base + p.spp;
     const int set_idx = (int)(&ws - sc->ws.sets);
     // HIP events around the isect launches (the roofline kernel); every other
     // launch only with SPT_FLAG_TIMING_ALL (each event pair costs host time).
@@ -2425,6 +2564,19 @@ retry_fit:
     // film slots follow the work order (film_slot)
     const uint32_t film_order = pixel_major;
     const auto resolve = [&](uint32_t s0, uint32_t ns) {
+        if (accum) {
+            ResolveAccumArgs ra{};
+            ra.sum = accum->sum; ra.sum_sq = accum->sum_sq; ra.film = accum->film; ra.variance = accum->variance;
+            ra.P = (uint32_t)P; ra.nsamples = ns;
+            ra.from_zero = s0 == 0;
+            ra.last = s0 + ns >= s_end;
+            ra.n_total = s_end;
+            ra.order = film_order;
+            ra.env_r = p.env[0]; ra.env_g = p.env[1]; ra.env_b = p.env[2];
+            ra.unwritten = &slot->dev->unwritten;
+            return mode == kModeUnit ? launch_resolve_flags_accum(sflag, ra, stream)
+                                     : launch_resolve_accum(sfilm, ra, stream);
+        }
         return mode == kModeUnit
                    ? launch_resolve_flags(sflag, acc, film_dev, (uint32_t)P, ns, s0 == 0, s0 + ns >= p.spp, p.spp,
                                           p.env[0], p.env[1], p.env[2], film_order, &slot->dev->unwritten, stream)
@@ -2541,7 +2693,7 @@ retry_fit:
         S.sfilm = sfilm;
         S.sflag = sflag;
         S.sample_jump = jumps;
-        S.cast_jump = jumps + p.spp;
+        S.cast_jump = cjumps;
         S.initstate = p.rng_initstate;
         S.P = (uint32_t)P; S.W = p.width; S.max_depth = p.max_depth;
         S.xcd_remap = (cfg.xcd_remap >> 1) & 1u;
@@ -2577,7 +2729,7 @@ retry_fit:
             D.sc = sc->dev();
             D.cam = cam;
             D.sample_jump = jumps;
-            D.cast_jump = jumps + p.spp;
+            D.cast_jump = cjumps;
             D.sfilm = sfilm;
             D.sflag = sflag;
             D.stats = slot->dev->stats;
@@ -2606,7 +2758,7 @@ retry_fit:
         F.sc = sc->dev();
         F.cam = cam;
         F.sample_jump = jumps;
-        F.cast_jump = jumps + p.spp;
+        F.cast_jump = cjumps;
         F.sfilm = sfilm;
         F.sflag = sflag;
         F.stats = slot->dev->stats;
@@ -2625,8 +2777,8 @@ retry_fit:
         F.grid_q8 = cfg.fused_grid_q8;
         F.env_r = p.env[0]; F.env_g = p.env[1]; F.env_b = p.env[2];
         uint32_t lanes = 0;
-        for (uint32_t s0 = 0; s0 < p.spp; s0 += chunk) {
-            const uint32_t ns = std::min(chunk, p.spp - s0);
+        for (uint32_t s0 = s_begin; s0 < s_end; s0 += chunk) {
+            const uint32_t ns = std::min(chunk, s_end - s0);
             F.work0 = (uint64_t)s0 * P;
             F.count = (uint32_t)((uint64_t)ns * P);  // <= 4 GiB / 12 B per chunk
             F.sample0 = s0;
@@ -2641,8 +2793,8 @@ retry_fit:
         C = lanes;
         rs.paths_in_flight = lanes;
     }
-    for (uint32_t s0 = 0; s0 < p.spp && !fused; s0 += chunk) {
-        const uint32_t ns = std::min(chunk, p.spp - s0);
+    for (uint32_t s0 = s_begin; s0 < s_end && !fused; s0 += chunk) {
+        const uint32_t ns = std::min(chunk, s_end - s0);
         const uint64_t w0 = (uint64_t)s0 * P, L = (uint64_t)ns * P;
         HIP_TRY(clear_film(ns));
         // fork: the sub-wavefront streams start after everything queued so far
@@ -2920,6 +3072,28 @@ retry_fit:
     slot->pending = true;
     *ticket_out = slot->ticket;
     return SPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+spt_status spt_render_async(spt_scene sc, const spt_render_params* pp, float* film_dev, void* caller,
+                            uint64_t* ticket_out) {
+    return render_enqueue(sc, pp, film_dev, nullptr, false, caller, ticket_out);
+}
+
+spt_status spt_render_accum_async(spt_scene sc, const spt_render_params* pp, const spt_accum* acc, void* caller,
+                                  uint64_t* ticket_out) {
+    return render_enqueue(sc, pp, nullptr, acc, true, caller, ticket_out);
+}
+
+spt_status spt_render_accum(spt_scene sc, const spt_render_params* pp, const spt_accum* acc,
+                            spt_render_stats* stats_out, void* stream) {
+    uint64_t ticket = 0;
+    spt_status st = spt_render_accum_async(sc, pp, acc, stream, &ticket);
+    if (st) return st;
+    return spt_render_wait(sc, ticket, stats_out);
 }
 
 spt_status spt_render_wait(spt_scene sc, uint64_t ticket, spt_render_stats* stats_out) {

@@ -1778,6 +1778,96 @@ __global__ __launch_bounds__(256) void resolve_flags_kernel(const uint8_t* __res
     }
 }
 
+// spt_render_accum's tail (spt.h): film = sum / n and the variance of the
+// pixel mean, every operation rounded to f32 (-ffp-contract=off).
+__device__ __forceinline__ void accum_finish(const ResolveAccumArgs& a, size_t i, float sum, float sq) {
+    const float n = (float)a.n_total;
+    const float m = sum / n;
+    if (a.film) a.film[i] = m;
+    if (a.variance) {
+        const float q = sq / n;
+        a.variance[i] = a.n_total < 2u ? 0.0f : fmaxf(q - m * m, 0.0f) / (float)(a.n_total - 1u);
+    }
+}
+
+// resolve_kernel for spt_render_accum: the caller's running sums are the
+// first chunk's start (0 when from_zero), the sum of x and of x * x come from
+// the one read of each slot, in sample order, and the last chunk also writes
+// film and variance.  sum_sq, film and variance may be null.
+__global__ __launch_bounds__(256) void resolve_accum_kernel(const float* __restrict__ sfilm, ResolveAccumArgs a) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.P) return;
+    const size_t P = a.P;
+    const bool sq = a.sum_sq != nullptr;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, q0 = 0.0f, q1 = 0.0f, q2 = 0.0f;
+    if (!a.from_zero) {
+        s0 = a.sum[p]; s1 = a.sum[P + p]; s2 = a.sum[2 * P + p];
+        if (sq) { q0 = a.sum_sq[p]; q1 = a.sum_sq[P + p]; q2 = a.sum_sq[2 * P + p]; }
+    }
+    uint32_t lost = 0;
+    for (uint32_t s = 0; s < a.nsamples; s++) {
+        size_t cs;
+        const float* x = film_rgb(const_cast<float*>(sfilm), s, p, a.P, a.nsamples, a.order, cs);
+        const float x0 = x[0], x1 = x[cs], x2 = x[2 * cs];
+        if (f2u(x0) == kFilmSentinel) lost++;
+        s0 = s0 + x0; s1 = s1 + x1; s2 = s2 + x2;
+        q0 = q0 + x0 * x0; q1 = q1 + x1 * x1; q2 = q2 + x2 * x2;
+    }
+    a.sum[p] = s0; a.sum[P + p] = s1; a.sum[2 * P + p] = s2;
+    if (sq) { a.sum_sq[p] = q0; a.sum_sq[P + p] = q1; a.sum_sq[2 * P + p] = q2; }
+    if (a.last) {
+        accum_finish(a, p, s0, q0);
+        accum_finish(a, P + p, s1, q1);
+        accum_finish(a, 2 * P + p, s2, q2);
+    }
+    if (lost) atomicAdd(a.unwritten, (unsigned long long)lost);
+}
+
+// resolve_flags_kernel for spt_render_accum (unit mode): a sample adds env[c]
+// or 0, so its square adds env[c] * env[c] or 0; adding the 0 leaves either sum
+// as it is, and k escapes are k additions, as in resolve_flags_kernel.
+__global__ __launch_bounds__(256) void resolve_flags_accum_kernel(const uint8_t* __restrict__ sflag,
+                                                                  ResolveAccumArgs a) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.P) return;
+    const uint32_t nsamples = a.nsamples;
+    uint32_t k = 0, lost = 0;
+    if (a.order && nsamples % 16u == 0u) {
+        // pixel-major: 16 flag bytes per read (resolve_flags_kernel)
+        const uint4* f4 = reinterpret_cast<const uint4*>(sflag + (size_t)p * nsamples);
+        for (uint32_t c = 0; c < nsamples / 16u; c++) {
+            const uint4 w = f4[c];
+            const uint32_t hi = __popc(w.x & 0x80808080u) + __popc(w.y & 0x80808080u) + __popc(w.z & 0x80808080u) +
+                                __popc(w.w & 0x80808080u);
+            const uint32_t lo = __popc(w.x & 0x01010101u) + __popc(w.y & 0x01010101u) + __popc(w.z & 0x01010101u) +
+                                __popc(w.w & 0x01010101u);
+            lost += hi;
+            k += lo - hi;
+        }
+    } else {
+        for (uint32_t s = 0; s < nsamples; s++) {
+            const uint32_t f = sflag[film_slot(s, p, a.P, nsamples, a.order)];
+            lost += f == kFlagSentinel ? 1u : 0u;
+            k += f == 1u ? 1u : 0u;
+        }
+    }
+    if (lost) atomicAdd(a.unwritten, (unsigned long long)lost);
+    const float env[3] = {a.env_r, a.env_g, a.env_b};
+    for (uint32_t c = 0; c < 3; c++) {
+        const size_t i = (size_t)c * a.P + p;
+        const float e = env[c], ee = e * e;
+        float sum = a.from_zero ? 0.0f : a.sum[i];
+        float sq = a.from_zero || !a.sum_sq ? 0.0f : a.sum_sq[i];
+        for (uint32_t j = 0; j < k; j++) {
+            sum = sum + e;
+            sq = sq + ee;
+        }
+        a.sum[i] = sum;
+        if (a.sum_sq) a.sum_sq[i] = sq;
+        if (a.last) accum_finish(a, i, sum, sq);
+    }
+}
+
 // optix_backend.h:462-486 + main.cpp:325 for the public ABI.
 __global__ __launch_bounds__(256) void hit_info_kernel(HitInfoArgs a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -2192,6 +2282,18 @@ hipError_t launch_resolve_flags(const uint8_t* sflag, float* acc, float* out, ui
     if (P == 0) return hipSuccess;
     hipLaunchKernelGGL(resolve_flags_kernel, dim3(blocks_for(P, 256)), dim3(256), 0, s, sflag, acc, out, P, nsamples,
                        first_chunk, last_chunk, spp, env_r, env_g, env_b, order, unwritten);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_accum(const float* sfilm, const ResolveAccumArgs& a, hipStream_t s) {
+    if (a.P == 0) return hipSuccess;
+    hipLaunchKernelGGL(resolve_accum_kernel, dim3(blocks_for(a.P, 256)), dim3(256), 0, s, sfilm, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_flags_accum(const uint8_t* sflag, const ResolveAccumArgs& a, hipStream_t s) {
+    if (a.P == 0) return hipSuccess;
+    hipLaunchKernelGGL(resolve_flags_accum_kernel, dim3(blocks_for(a.P, 256)), dim3(256), 0, s, sflag, a);
     return hipGetLastError();
 }
 

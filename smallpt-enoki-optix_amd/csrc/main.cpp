@@ -21,6 +21,7 @@
 //                  [--wavefront paths] [--rr depth] [--rng-x-first] [--device N] [--save-cache f.sptc]
 //                  [--gpus N] [--rows-per-group R] [--rehearse-shared-gpu]
 //                  [--aov PREFIX] [--denoise [--denoise-iters N]]
+//                  [--passes N] [--variance FILE] [--denoise-var]
 //
 // --aov PREFIX writes the first-hit buffers of the render (spt_render_aov) as
 // PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm (depth in all three
@@ -28,6 +29,14 @@
 // spt_denoise (default sigmas, --denoise-iters iterations) guided by those
 // buffers: the denoised image goes to -o, the raw one to <out>.raw.pfm.
 // Single-device only: neither combines with --gpus above 1.
+//
+// --passes N renders N passes of -s samples each with spt_render_accum (the
+// image is the accumulated film: the same bytes as one render of N x s
+// samples).  --variance FILE writes the per-channel variance of the pixel mean
+// as a PFM.  --denoise-var filters the image with spt_denoise_var, guided by
+// that variance and the first-hit buffers as --denoise is (raw image to
+// <out>.raw.pfm; --denoise-iters applies); it implies the second moments.
+// Single-device too.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -205,7 +214,9 @@ int main(int argc, char** argv) {
     std::string obj = "mitsuba.obj";  // main.cpp:365
     std::string out = "wurst.pfm";    // main.cpp:442
     std::string cache_out, aov_prefix;
-    bool do_denoise = false;
+    bool do_denoise = false, do_denoise_var = false;
+    std::string variance_out;
+    int passes = 0;  // 0: one spt_render
     int denoise_iters = -1;  // -1: spt_default_denoise_params
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
@@ -235,21 +246,36 @@ int main(int argc, char** argv) {
         else if (a == "--aov") aov_prefix = next();
         else if (a == "--denoise") do_denoise = true;
         else if (a == "--denoise-iters") denoise_iters = std::atoi(next());
+        else if (a == "--denoise-var") do_denoise_var = true;
+        else if (a == "--passes") passes = std::atoi(next());
+        else if (a == "--variance") variance_out = next();
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
     }
     if (ngpu < 0 || rows_per_group == 0) { std::cerr << "--gpus must be >= 1, --rows-per-group >= 1\n"; return 2; }
-    const bool want_aov = !aov_prefix.empty() || do_denoise;
+    const bool want_aov = !aov_prefix.empty() || do_denoise || do_denoise_var;
     if (want_aov && ngpu > 1) {
         std::cerr << "--aov / --denoise render on one device: not with --gpus " << ngpu
                   << " (the multi-GPU gather of the feature buffers is not implemented)\n";
         return 2;
     }
-    if (denoise_iters > 8 || (denoise_iters >= 0 && !do_denoise)) {
-        std::cerr << "--denoise-iters takes 0..8 and goes with --denoise\n";
+    if (passes < 0 || ((passes > 0 || !variance_out.empty()) && ngpu > 1)) {
+        std::cerr << "--passes takes N >= 1; --passes / --variance render on one device: not with --gpus above 1\n";
         return 2;
     }
-    if (want_aov && ngpu == 1) ngpu = 0;  // one tile: the single-device path below (the same image)
+    if (do_denoise && do_denoise_var) {
+        std::cerr << "--denoise and --denoise-var: choose one\n";
+        return 2;
+    }
+    if (denoise_iters > 8 || (denoise_iters >= 0 && !do_denoise && !do_denoise_var)) {
+        std::cerr << "--denoise-iters takes 0..8 and goes with --denoise / --denoise-var\n";
+        return 2;
+    }
+    // the accumulating path: asked for, or needed for the variance
+    const bool accum = passes > 0 || !variance_out.empty() || do_denoise_var;
+    const bool moments = !variance_out.empty() || do_denoise_var;
+    if (passes == 0) passes = 1;
+    if ((want_aov || accum) && ngpu == 1) ngpu = 0;  // one tile: the single-device path below (the same image)
     try {
         const bool cache = spt::ends_with(obj, ".sptc");
         std::unique_ptr<spt::Mesh> mesh;
@@ -295,14 +321,47 @@ int main(int argc, char** argv) {
         } else {
             float* film = nullptr;
             hip_check(hipMalloc((void**)&film, sizeof(float) * 3 * npx), "hipMalloc film");
+            // spt_render_accum's planes: sum, sum_sq, variance (the film is `film`)
+            std::unique_ptr<spt::DeviceFloats> sums, sums_sq, variance;
+            // the feature buffers line up with the samples of one render of every pass's samples
+            spt_render_params whole = p;
             auto t0 = clock_t_::now();
-            scene.render(p, film, &st);    // main.cpp:385-429
+            if (accum) {
+                if ((uint64_t)p.spp * (uint64_t)passes >= (1ull << 24))
+                    throw std::runtime_error("--passes x -s must stay below 2^24 samples");
+                whole.spp = p.spp * (uint32_t)passes;
+                sums.reset(new spt::DeviceFloats(3 * npx));
+                if (moments) {
+                    sums_sq.reset(new spt::DeviceFloats(3 * npx));
+                    variance.reset(new spt::DeviceFloats(3 * npx));
+                }
+                spt_accum acc{};
+                acc.sum = sums->get();
+                acc.sum_sq = moments ? sums_sq->get() : nullptr;
+                acc.film = film;
+                acc.variance = moments ? variance->get() : nullptr;
+                for (int k = 0; k < passes; k++) {
+                    spt_render_stats ps{};
+                    acc.sample_base = (uint32_t)k * p.spp;
+                    scene.render_accum(p, acc, &ps);
+                    st.paths += ps.paths;
+                    st.ray_casts += ps.ray_casts;
+                }
+            } else {
+                scene.render(p, film, &st);    // main.cpp:385-429
+            }
             ms = ms_since(t0);
             std::cout << ms << std::endl;  // main.cpp:431
+            if (!variance_out.empty()) {
+                const std::vector<float> v = variance->to_host();
+                spt::check(spt_pfm_write(variance_out.c_str(), v.data(), v.data() + npx, v.data() + 2 * npx, p.width,
+                                         p.height),
+                           "spt_pfm_write");
+            }
             hip_check(hipMemcpy(host.data(), film, sizeof(float) * 3 * npx, hipMemcpyDeviceToHost), "hipMemcpy film");
             if (want_aov) {
                 spt::AovBuffers aov(npx);
-                scene.render_aov(p, aov.planes());
+                scene.render_aov(whole, aov.planes());
                 if (!aov_prefix.empty()) {
                     const std::vector<float> a = aov.to_host();  // albedo r g b, normal x y z, depth, coverage
                     const float* d = a.data();
@@ -325,6 +384,19 @@ int main(int argc, char** argv) {
                     if (denoise_iters >= 0) dp.iterations = (uint32_t)denoise_iters;
                     spt::DeviceFloats clean(3 * npx);
                     spt::denoise(dp, film, &aov.planes(), clean.get());
+                    host = clean.to_host();
+                }
+                if (do_denoise_var) {
+                    spt::check(spt_pfm_write((out + ".raw.pfm").c_str(), host.data(), host.data() + npx,
+                                             host.data() + 2 * npx, p.width, p.height),
+                               "spt_pfm_write");
+                    spt_denoise_var_params dp;
+                    spt_default_denoise_var_params(&dp);
+                    dp.width = p.width;
+                    dp.height = p.height;
+                    if (denoise_iters >= 0) dp.iterations = (uint32_t)denoise_iters;
+                    spt::DeviceFloats clean(3 * npx);
+                    spt::denoise_var(dp, film, variance->get(), &aov.planes(), clean.get());
                     host = clean.to_host();
                 }
             }

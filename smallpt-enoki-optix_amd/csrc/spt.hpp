@@ -87,6 +87,12 @@ class Scene {
     void render(const spt_render_params& p, float* film_dev, spt_render_stats* stats, void* stream = nullptr) {
         check(spt_render(scene_, &p, film_dev, stats, stream), "spt_render");
     }
+    // spt_render_accum: samples [acc.sample_base, acc.sample_base + p.spp) added
+    // onto the caller's running sums (progressive rendering)
+    void render_accum(const spt_render_params& p, const spt_accum& acc, spt_render_stats* stats,
+                      void* stream = nullptr) {
+        check(spt_render_accum(scene_, &p, &acc, stats, stream), "spt_render_accum");
+    }
     // spt_render_aov: the first-hit buffers of p's tile, queued on `stream`
     void render_aov(const spt_render_params& p, const spt_aov& planes, void* stream = nullptr) {
         check(spt_render_aov(scene_, &p, &planes, stream), "spt_render_aov");
@@ -179,6 +185,17 @@ inline void denoise(const spt_denoise_params& p, const float* color, const spt_a
     DeviceFloats scratch(spt_denoise_scratch_bytes(p.width, p.height) / sizeof(float));
     check(spt_denoise(&p, color, guides, out, scratch.get(), stream), "spt_denoise");
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) throw std::runtime_error("spt::denoise: stream failed");
+}
+
+// spt_denoise_var with its scratch allocated for the call: color, variance,
+// out = 3 planes (out must not alias an input); guides and variance_out may be
+// NULL.  Synchronises `stream` before the scratch is freed.
+inline void denoise_var(const spt_denoise_var_params& p, const float* color, const float* variance,
+                        const spt_aov* guides, float* out, float* variance_out = nullptr, void* stream = nullptr) {
+    DeviceFloats scratch(spt_denoise_var_scratch_bytes(p.width, p.height) / sizeof(float));
+    check(spt_denoise_var(&p, color, variance, guides, out, variance_out, scratch.get(), stream), "spt_denoise_var");
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+        throw std::runtime_error("spt::denoise_var: stream failed");
 }
 
 }  // namespace spt

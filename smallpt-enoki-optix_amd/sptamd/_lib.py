@@ -39,6 +39,8 @@ EXPORTED = [
     "spt_debug_fail_workspace_alloc",
     "spt_render_aov", "spt_default_denoise_params", "spt_denoise_scratch_bytes", "spt_denoise",
     "spt_scene_update_geometry", "spt_scene_update_geometry_device", "spt_scene_get_refit_stats",
+    "spt_render_accum", "spt_render_accum_async",
+    "spt_default_denoise_var_params", "spt_denoise_var_scratch_bytes", "spt_denoise_var",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -175,6 +177,18 @@ class DenoiseParams(ctypes.Structure):
                 ("sigma_depth", c_float)]
 
 
+class DenoiseVarParams(ctypes.Structure):
+    _fields_ = [("width", c_uint32), ("height", c_uint32), ("iterations", c_uint32),
+                ("sigma_variance", c_float), ("sigma_normal", c_float), ("sigma_albedo", c_float),
+                ("sigma_depth", c_float)]
+
+
+class Accum(ctypes.Structure):
+    """spt_accum: the running sums of spt_render_accum and what it derives from them."""
+    _fields_ = [("sample_base", c_uint32), ("reserved", c_uint32), ("sum", c_void_p), ("sum_sq", c_void_p),
+                ("film", c_void_p), ("variance", c_void_p)]
+
+
 def _load() -> ctypes.CDLL:
     # torch ships its own HIP runtime (SONAME libamdhip64.so.7).  Load it first
     # so libspt.so binds to that one copy: loading libspt.so first would map the
@@ -230,6 +244,11 @@ def _load() -> ctypes.CDLL:
         "spt_scene_update_geometry": (i32, [vp, vp, vp, u64, u64, vp, vp, u64]),
         "spt_scene_update_geometry_device": (i32, [vp, vp, vp, u64, u64, vp, vp, u64, vp]),
         "spt_scene_get_refit_stats": (i32, [vp, POINTER(RefitStats)]),
+        "spt_render_accum": (i32, [vp, POINTER(RenderParams), POINTER(Accum), POINTER(RenderStats), vp]),
+        "spt_render_accum_async": (i32, [vp, POINTER(RenderParams), POINTER(Accum), vp, POINTER(u64)]),
+        "spt_default_denoise_var_params": (None, [POINTER(DenoiseVarParams)]),
+        "spt_denoise_var_scratch_bytes": (ctypes.c_size_t, [u32, u32]),
+        "spt_denoise_var": (i32, [POINTER(DenoiseVarParams), vp, vp, POINTER(Aov), vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -255,6 +274,12 @@ def default_params() -> RenderParams:
 def default_denoise_params() -> DenoiseParams:
     p = DenoiseParams()
     lib.spt_default_denoise_params(ctypes.byref(p))
+    return p
+
+
+def default_denoise_var_params() -> DenoiseVarParams:
+    p = DenoiseVarParams()
+    lib.spt_default_denoise_var_params(ctypes.byref(p))
     return p
 
 
@@ -357,7 +382,8 @@ def tile_rows(height: int, tile_index: int, tile_count: int, rows_per_group: int
 
 __all__ = [
     "lib", "check", "SptError", "Rays", "Hits", "HitInfo", "Camera", "RenderParams", "RenderStats",
-    "SceneStats", "RefitStats", "Mesh", "Config", "Aov", "AOV_PLANES", "DenoiseParams", "default_denoise_params", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
+    "SceneStats", "RefitStats", "Mesh", "Config", "Aov", "AOV_PLANES", "DenoiseParams", "default_denoise_params",
+    "DenoiseVarParams", "default_denoise_var_params", "Accum", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
     "LIB_PATH", "REPO_ROOT",
     "PCG32_DEFAULT_STATE", "SPT_RNG_Y_FIRST", "SPT_RNG_X_FIRST", "SPT_FLAG_TIMING", "c_uint8",
 ]

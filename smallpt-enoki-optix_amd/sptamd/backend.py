@@ -535,6 +535,13 @@ class Scene:
         check(lib.spt_render_wait(self.backend.handle, ticket, ctypes.byref(st)), "spt_render_wait")
         return st.as_dict()
 
+    def accumulator(self, params: RenderParams, moments: bool = True) -> "Accumulator":
+        """A progressive render of params' tile (spt_render_accum): an object
+        that owns the running sums and adds passes of samples to them.
+        params.spp is not used (each add names its own count); moments=False
+        keeps no sum of squares (no variance)."""
+        return Accumulator(self, params, moments)
+
     def render_aov(self, params: RenderParams, planes: Sequence[str] = ("albedo", "normal", "depth", "coverage"),
                    stream=None, out: Optional[dict] = None) -> dict:
         """spt_render_aov: the first-hit buffers of params' tile, lined up with
@@ -594,6 +601,65 @@ class Scene:
         return film
 
 
+class Accumulator:
+    """Scene.accumulator: the planes of one spt_render_accum accumulation.
+
+    add(spp) renders the next spp samples of every tile pixel and returns the
+    pass's stats; add_async / wait are the queued pair (passes queued on one
+    stream need no synchronisation in between).  film, variance, sum and sum_sq
+    are (3, rows, W) float32 device tensors, current once the last pass has run
+    on its stream; any split of N samples into passes gives the same bits, and
+    film is Scene.render's at spp = N (include/spt.h)."""
+
+    def __init__(self, scene: "Scene", params: RenderParams, moments: bool = True):
+        self.scene = scene
+        self.params = RenderParams.from_buffer_copy(params)
+        rows = _lib.tile_row_count(params.height, params.tile_index, params.tile_count, params.rows_per_group)
+        shape, dev = (3, rows, params.width), scene.backend.device
+        self.sum = torch.zeros(shape, dtype=torch.float32, device=dev)
+        self.film = torch.zeros(shape, dtype=torch.float32, device=dev)
+        self.sum_sq = torch.zeros(shape, dtype=torch.float32, device=dev) if moments else None
+        self.variance = torch.zeros(shape, dtype=torch.float32, device=dev) if moments else None
+        self.samples = 0
+
+    def reset(self) -> None:
+        """Start over: the next add renders sample 0 (the planes are rewritten by it)."""
+        self.samples = 0
+
+    def _acc(self, spp: int) -> _lib.Accum:
+        if spp <= 0:
+            raise ValueError("Accumulator.add: spp must be > 0")
+        self.params.spp = spp
+        a = _lib.Accum()
+        a.sample_base = self.samples
+        a.sum, a.film = self.sum.data_ptr(), self.film.data_ptr()
+        if self.sum_sq is not None:
+            a.sum_sq, a.variance = self.sum_sq.data_ptr(), self.variance.data_ptr()
+        return a
+
+    def add(self, spp: int, stream=None) -> dict:
+        """Render samples [samples, samples + spp) onto the sums; returns the pass's stats."""
+        a, st = self._acc(spp), RenderStats()
+        self.scene.backend.sync_config()
+        check(lib.spt_render_accum(self.scene.backend.handle, ctypes.byref(self.params), ctypes.byref(a),
+                                   ctypes.byref(st), _stream_handle(stream)), "spt_render_accum")
+        self.samples += spp
+        return st.as_dict()
+
+    def add_async(self, spp: int, stream=None) -> int:
+        """Queue the pass and return its ticket (collect it with wait)."""
+        a, ticket = self._acc(spp), ctypes.c_uint64()
+        self.scene.backend.sync_config()
+        check(lib.spt_render_accum_async(self.scene.backend.handle, ctypes.byref(self.params), ctypes.byref(a),
+                                         _stream_handle(stream), ctypes.byref(ticket)), "spt_render_accum_async")
+        self.samples += spp
+        return ticket.value
+
+    def wait(self, ticket: int) -> dict:
+        """The stats of a queued pass (waits for it)."""
+        return self.scene.render_wait(ticket)
+
+
 def aov_struct(aov: Optional[dict]) -> _lib.Aov:
     """spt_aov over render_aov's dict (missing names: NULL planes)."""
     a = _lib.Aov()
@@ -641,6 +707,44 @@ def denoise(film: torch.Tensor, aov: Optional[dict] = None, iterations: int = 5,
     check(lib.spt_denoise(ctypes.byref(p), film.data_ptr(), ctypes.byref(guides), out.data_ptr(), scratch.data_ptr(),
                           s.cuda_stream or None), "spt_denoise")
     return out
+
+
+def denoise_var(film: torch.Tensor, variance: torch.Tensor, aov: Optional[dict] = None, iterations: int = 5,
+                sigma_variance: Optional[float] = None, sigma_normal: Optional[float] = None,
+                sigma_albedo: Optional[float] = None, sigma_depth: Optional[float] = None, stream=None,
+                out: Optional[torch.Tensor] = None, return_variance: bool = False):
+    """spt_denoise_var: the variance-guided a-trous filter of a whole (3, H, W)
+    film, its colour term in standard deviations of `variance` (the (3, H, W)
+    per-channel variance of the pixel mean, an Accumulator's), guided by
+    render_aov's dict like denoise.  Sigmas default to
+    spt_default_denoise_var_params; <= 0 disables a term.  Returns the filtered
+    film, or (film, (H, W) remaining variance) with return_variance."""
+    for t, name in ((film, "film"), (variance, "variance")):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 3 and t.shape[0] == 3, \
+            f"{name} must be a contiguous (3, H, W) float32 device tensor"
+    assert variance.shape == film.shape, "variance: not the film's size"
+    p = _lib.default_denoise_var_params()
+    p.height, p.width, p.iterations = int(film.shape[1]), int(film.shape[2]), iterations
+    for k, v in (("sigma_variance", sigma_variance), ("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo),
+                 ("sigma_depth", sigma_depth)):
+        if v is not None:
+            setattr(p, k, float(v))
+    for name in ("albedo", "normal", "depth"):
+        t = None if aov is None else aov.get(name)
+        assert t is None or tuple(t.shape[-2:]) == tuple(film.shape[1:]), f"{name}: not the film's size"
+    s = stream if stream is not None else torch.cuda.current_stream(film.device)
+    with torch.cuda.stream(s):
+        if out is None:
+            out = torch.empty_like(film)
+        vout = torch.empty(film.shape[1:], dtype=torch.float32, device=film.device) if return_variance else None
+        scratch = torch.empty(max(1, lib.spt_denoise_var_scratch_bytes(p.width, p.height)), dtype=torch.uint8,
+                              device=film.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == film.shape
+    guides = aov_struct(aov)
+    check(lib.spt_denoise_var(ctypes.byref(p), film.data_ptr(), variance.data_ptr(), ctypes.byref(guides),
+                              out.data_ptr(), None if vout is None else vout.data_ptr(), scratch.data_ptr(),
+                              s.cuda_stream or None), "spt_denoise_var")
+    return (out, vout) if return_variance else out
 
 
 def scene_cache_info(path: str) -> dict:
