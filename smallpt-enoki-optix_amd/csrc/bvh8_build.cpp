@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "bvh_build.h"
+#include "bvh_refit.h"
 
 namespace spt {
 namespace {
@@ -258,6 +259,8 @@ struct Collapser {
             } else if (ext > 0.0) {
                 e = (int)std::ceil(std::log2(ext / 255.0));
                 while (std::ldexp(255.0, e) < ext) e++;
+                // ext is rounded (a coordinate far below lo's ulp is lost in it): the exact plane decides
+                while (e < 127 && refit_plane_cmp(lo[a], std::ldexp(255.0, e), hi[a]) < 0) e++;
                 e = std::min(std::max(e, -100), 127);
             }
             ebias[a] = e + 127;
@@ -280,6 +283,10 @@ struct Collapser {
                 double step = std::ldexp(1.0, ebias[a] - 127);
                 double ql = std::floor(((double)kd.lo[a] - (double)lo[a]) / step);
                 double qh = std::ceil(((double)kd.hi[a] - (double)lo[a]) / step);
+                // the differences round when a coordinate lies far below lo's ulp: the bytes
+                // are held to the exact planes lo + q * step (bvh_refit.h refit_plane_cmp)
+                if (refit_plane_cmp(lo[a], ql * step, kd.lo[a]) > 0) ql -= 1.0;
+                if (refit_plane_cmp(lo[a], qh * step, kd.hi[a]) < 0) qh += 1.0;
                 if (!(ql >= 0.0)) ql = 0.0;  // NaN-safe
                 if (!(qh <= 255.0)) qh = 255.0;
                 if (ql > 255.0) ql = 255.0;

@@ -11,7 +11,8 @@
 // and gpu_build.hip collapse_emit_kernel: f32 fminf / fmaxf unions, the
 // frame (origin = the node's f32 lo, per-axis exponent ceil(log2(ext / 255))
 // with the ldexp fix-up, infinite or NaN extent -> 127) and the quantisation
-// in double, floor / ceil clamped to [0, 255], empty slots inverted (255 / 0).
+// in double, floor / ceil held to the exact planes lo + q * step and clamped to
+// [0, 255], empty slots inverted (255 / 0).
 // Topology words (meta bytes, tri_base, the child-group word, the imask, the
 // octant slot assignment) are never rewritten.
 #pragma once
@@ -119,6 +120,16 @@ SPT_HD void refit_kids2(const uint32_t* w, RefitKid kid[2]) {
 
 // ---- quantisation frame (bvh8_build.cpp emit())
 
+// The sign of (lo + m) - x in exact arithmetic (the sum's rounding error
+// recovered with Knuth's two-sum; s is the double nearest the exact sum, so
+// it decides unless it equals x).  The quantised planes lo + q * step are
+// compared with it: a difference such as kid.lo - lo rounds in double when a
+// coordinate lies far below lo's ulp, or lo far below the step.  0 with NaN.
+SPT_HD int refit_plane_cmp(double lo, double m, double x) {
+    const double s = lo + m, b = s - lo, err = (lo - (s - b)) + (m - b);
+    return s > x ? 1 : (s < x ? -1 : (s == x ? (err > 0.0 ? 1 : (err < 0.0 ? -1 : 0)) : 0));
+}
+
 SPT_HD int refit_ebias(float lo, float hi) {
     const double ext = (double)hi - (double)lo;
     int e = -100;
@@ -127,6 +138,7 @@ SPT_HD int refit_ebias(float lo, float hi) {
     } else if (ext > 0.0) {
         e = (int)ceil(log2(ext / 255.0));
         while (ldexp(255.0, e) < ext) e++;
+        while (e < 127 && refit_plane_cmp(lo, ldexp(255.0, e), hi) < 0) e++;  // ext is rounded: the exact plane
         e = e < -100 ? -100 : (e > 127 ? 127 : e);
     }
     return e + 127;
@@ -137,6 +149,8 @@ SPT_HD void refit_quant(const RefitBox& kid, const RefitBox& node, const int ebi
         const double step = ldexp(1.0, ebias[a] - 127);
         double l = floor(((double)kid.lo[a] - (double)node.lo[a]) / step);
         double h = ceil(((double)kid.hi[a] - (double)node.lo[a]) / step);
+        if (refit_plane_cmp(node.lo[a], l * step, kid.lo[a]) > 0) l -= 1.0;  // held to the exact planes
+        if (refit_plane_cmp(node.lo[a], h * step, kid.hi[a]) < 0) h += 1.0;
         if (!(l >= 0.0)) l = 0.0;  // NaN-safe
         if (!(h <= 255.0)) h = 255.0;
         if (l > 255.0) l = 255.0;

@@ -23,6 +23,7 @@
 #include "bvh_build.h"
 #include "gpu_build.h"
 #include "spt_internal.h"
+#include "bvh_refit.h"
 
 namespace spt {
 namespace {
@@ -454,6 +455,8 @@ __global__ __launch_bounds__(kBlock) void collapse_emit_kernel(EmitArgs a) {
         } else if (ext > 0.0) {
             ex = (int)ceil(log2(ext / 255.0));
             while (ldexp(255.0, ex) < ext) ex++;
+            // ext is rounded (a coordinate far below lo's ulp is lost in it): the exact plane decides
+            while (ex < 127 && refit_plane_cmp(lo[ax], ldexp(255.0, ex), hi[ax]) < 0) ex++;
             ex = min(max(ex, -100), 127);
         }
         ebias[ax] = ex + 127;
@@ -477,6 +480,9 @@ __global__ __launch_bounds__(kBlock) void collapse_emit_kernel(EmitArgs a) {
             const double step = ldexp(1.0, ebias[ax] - 127);
             double ql = floor(((double)kl[ax] - (double)lo[ax]) / step);
             double qh = ceil(((double)kh[ax] - (double)lo[ax]) / step);
+            // (bvh8_build.cpp emit(): held to the exact planes lo + q * step, the differences above round)
+            if (refit_plane_cmp(lo[ax], ql * step, kl[ax]) > 0) ql -= 1.0;
+            if (refit_plane_cmp(lo[ax], qh * step, kh[ax]) < 0) qh += 1.0;
             if (!(ql >= 0.0)) ql = 0.0;
             if (!(qh <= 255.0)) qh = 255.0;
             if (ql > 255.0) ql = 255.0;

@@ -18,6 +18,7 @@
 
 #include "bvh_build.h"
 #include "bvh_refit.h"
+#include "node6.h"
 
 using namespace spt;
 
@@ -63,37 +64,11 @@ std::vector<float> records(const std::vector<float>& tv, const std::vector<uint3
     return rec;
 }
 
-// The compact 80-B node as the 64-B node (bvh_build.h): the non-empty slots
-// become children 0..5 in slot order, the group word is the first inner child.
-std::vector<uint32_t> to_node6(const std::vector<uint32_t>& n8) {
-    const size_t nn = n8.size() / 20;
-    std::vector<uint32_t> out(nn * 16, 0u);
-    for (size_t i = 0; i < nn; i++) {
-        const uint32_t* w = &n8[i * 20];
-        uint32_t meta[6] = {0, 0, 0, 0, 0, 0}, q[6][6];
-        for (int p = 0; p < 6; p++)
-            for (int c = 0; c < 6; c++) q[p][c] = (p & 1) ? 0u : 255u;
-        int c = 0;
-        for (uint32_t s = 0; s < 8; s++) {
-            const uint32_t sh = (s & 3u) * 8u, m = (w[6 + (s >> 2)] >> sh) & 0xffu;
-            if (!m) continue;
-            if (c == 6) { expect(false, "more than six children", 6, nn); break; }
-            meta[c] = m;
-            for (int a = 0; a < 3; a++) {
-                q[2 * a][c] = (w[8 + 2 * a + (s >> 2)] >> sh) & 0xffu;
-                q[2 * a + 1][c] = (w[14 + 2 * a + (s >> 2)] >> sh) & 0xffu;
-            }
-            c++;
-        }
-        uint32_t* o = &out[i * 16];
-        o[0] = w[0]; o[1] = w[1]; o[2] = w[2]; o[3] = w[5];
-        o[4] = meta[0] | meta[1] << 8 | meta[2] << 16 | meta[3] << 24;
-        o[5] = meta[4] | meta[5] << 8 | (w[3] & 0xffu) << 16 | ((w[3] >> 8) & 0xffu) << 24;
-        o[6] = w[4] | ((w[3] >> 16) & 0xffu) << 24;
-        for (int p = 0; p < 6; p++) o[7 + p] = q[p][0] | q[p][1] << 8 | q[p][2] << 16 | q[p][3] << 24;
-        for (int a = 0; a < 3; a++)
-            o[13 + a] = q[2 * a][4] | q[2 * a][5] << 8 | q[2 * a + 1][4] << 16 | q[2 * a + 1][5] << 24;
-    }
+// the compact 80-B nodes as 64-B nodes (node6.h)
+std::vector<uint32_t> node6_of(const std::vector<uint32_t>& n8) {
+    bool over = false;
+    std::vector<uint32_t> out = to_node6(n8, &over);
+    expect(!over, "more than six children", 6, n8.size() / 20);
     return out;
 }
 
@@ -216,7 +191,7 @@ void run(int fmt, uint64_t n, uint64_t seed) {
         t.shift = 0;
     } else {
         Bvh8BuildResult b = build_bvh8(tv.data(), n, false, fmt);
-        t.nodes = fmt == kRefitFmt6 ? to_node6(b.nodes) : b.nodes;
+        t.nodes = fmt == kRefitFmt6 ? node6_of(b.nodes) : b.nodes;
         slot2tri = b.slot2tri;
         t.stride = fmt == kRefitFmt6 ? 16 : 20;
         t.shift = kRefitCompact;

@@ -401,6 +401,59 @@ def test_smallest_trees(width, name):
             assert (rt >= 0).any()
 
 
+NF_RAYS = 4096
+
+
+@functools.lru_cache(maxsize=None)
+def non_finite_pos():
+    """deformed_pos(0.7) with one triangle all NaN, one +inf and one -inf coordinate."""
+    pos = np.array(deformed_pos(0.7), copy=True)
+    pt = np.asarray(base_mesh()["pos_tri"], np.int64).reshape(-1, 3)
+    broken = pt[[5, 600, 6000]]
+    pos[broken[0]] = np.nan
+    pos[broken[1, 0], 0] = np.inf
+    pos[broken[2, 1], 2] = -np.inf
+    pos.setflags(write=False)
+    return pos
+
+
+@functools.lru_cache(maxsize=None)
+def non_finite_oracle_hits():
+    """The brute-force oracle (no tree) over the first NF_RAYS rays on the mesh
+    of non_finite_pos() without its broken triangles: (ids in the full mesh's
+    numbering, t, the broken triangles)."""
+    m = mesh_at(None)
+    pos = non_finite_pos()
+    pt = np.asarray(m["pos_tri"], np.int64).reshape(-1, 3)
+    nt = np.asarray(m["nrm_tri"], np.int64).reshape(-1, 3)
+    bad = ~np.isfinite(pos[pt]).all(axis=(1, 2))
+    keep = np.flatnonzero(~bad)
+    used = np.zeros(len(pos), bool)
+    used[pt[keep]] = True                                # vertices only the broken triangles use may be non-finite
+    clean = dict(m, pos=np.where(used[:, None], pos, np.float32(0.0)), pos_tri=pt[keep].astype(np.int32),
+                 nrm_tri=nt[keep].astype(np.int32), mat_id=np.asarray(m["mat_id"])[keep])
+    clean.pop("tc_tri", None)
+    clean.pop("tc", None)
+    o, d = rays()
+    rt, rtt, _, _ = O.OracleScene(clean, use_bvh=False).intersect(o[:, :NF_RAYS], d[:, :NF_RAYS])
+    return np.where(rt >= 0, keep[np.maximum(rt, 0)], -1).astype(np.int32), rtt, np.flatnonzero(bad)
+
+
+def assert_non_finite_hits(s):
+    """Every finite triangle is still reachable: ids and t over the first
+    NF_RAYS rays equal the brute-force oracle's on the mesh without the broken
+    triangles."""
+    o, d = rays()
+    o, d = np.ascontiguousarray(o[:, :NF_RAYS]), np.ascontiguousarray(d[:, :NF_RAYS])
+    tri, t, _, _ = s.backend.intersect_raw(sptamd.Ray3.make(o, d))
+    torch.cuda.synchronize()
+    rt, rtt, _ = non_finite_oracle_hits()
+    hit = rt >= 0
+    assert hit.mean() >= 0.2, hit.mean()                 # a fair share of the rays hits (else: other rays)
+    np.testing.assert_array_equal(tri.cpu().numpy(), rt)
+    np.testing.assert_array_equal(t.cpu().numpy()[hit], rtt[hit])
+
+
 def test_non_finite_positions_do_not_fault():
     """Infinite and NaN coordinates are taken as the builders take them (the
     widest quantisation step; such triangles are never hit)."""
@@ -412,6 +465,7 @@ def test_non_finite_positions_do_not_fault():
     pos[broken[0]] = np.nan
     pos[broken[1, 0], 0] = np.inf
     pos[broken[2, 1], 2] = -np.inf
+    assert np.array_equal(pos, non_finite_pos(), equal_nan=True)
     s.update_geometry(pos, m["nrm"])
     got, st = film_of(s)
     assert np.isfinite(got).all() and st["film_slots_unwritten"] == 0
@@ -419,6 +473,8 @@ def test_non_finite_positions_do_not_fault():
     tri = s.backend.intersect_raw(sptamd.Ray3.make(o, d))[0].cpu().numpy()
     bad_tris = np.flatnonzero(~np.isfinite(pos[pt]).all(axis=(1, 2)))
     assert len(bad_tris) >= 3 and not np.isin(tri, bad_tris).any()
+    assert np.array_equal(bad_tris, non_finite_oracle_hits()[2])
+    assert_non_finite_hits(s)                              # and every finite triangle is still reachable
     s.update_geometry(deformed_pos(0.7), m["nrm"])         # and the tree recovers
     assert_film(s, 0.7, msg="after the non-finite update")
 

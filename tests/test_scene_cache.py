@@ -7,40 +7,13 @@ byte in any section, another version or layout, inconsistent sizes, a
 truncated or over-long file — is refused with SPT_ERR_INVALID, a missing file
 with SPT_ERR_IO.  The GPU round trips are tests/test_gpu_scene_cache.py."""
 import ctypes
-from ctypes import c_char, c_uint32, c_uint64
 
 import numpy as np
 import pytest
 
 import sptamd
+from bvh_audit import CACHE_VERSION, NODE6_QUADS, SECTIONS, TRI_QUADS, Header, tri_records  # the documented layout
 from sptamd import _lib
-
-SECTIONS = ["nodes", "triangles", "normals", "texcoords", "orig2slot", "albedo", "emission", "spheres",
-            "sphere materials", "material kinds", "texture sizes", "texels", "extra"]
-TRI_QUADS, NODE6_QUADS = 4, 4   # spt_internal.h kTriQuads / kNode6Quads
-CACHE_VERSION = 2               # capi.cpp kCacheVersion (2: 64-B rotated triangle records)
-
-
-def tri_records(v9, ids):
-    """spt_internal.h tri_record_fill: per triangle 16 floats, each vertex as
-    x y z x y, the original id's bits in float 15."""
-    v = np.asarray(v9, np.float32).reshape(-1, 3, 3)
-    rec = np.zeros((v.shape[0], 16), np.float32)
-    for k in range(3):
-        rec[:, 5 * k:5 * k + 3] = v[:, k]
-        rec[:, 5 * k + 3:5 * k + 5] = v[:, k, :2]
-    rec[:, 15] = np.asarray(ids, np.uint32).view(np.float32)
-    return rec
-
-
-class Header(ctypes.Structure):
-    _fields_ = ([("magic", c_char * 8)] +
-                [(n, c_uint32) for n in ("version", "header_bytes", "tri_quads", "node_quads", "node6",
-                                         "group_shift", "config_bytes", "stats_bytes", "stack_depth", "nmat",
-                                         "nemit", "nsph", "nkind", "ntexmat")] +
-                [("ntri", c_uint64), ("bytes", c_uint64 * 13), ("sum", c_uint64 * 13),
-                 ("cfg", _lib.Config), ("stats", _lib.SceneStats)])
-
 
 M, MASK = 0x9FB21C651E98DF25, (1 << 64) - 1
 
