@@ -357,13 +357,17 @@ typedef struct spt_config {
 
 void spt_default_config(spt_config* cfg);
 
-/* spt_scene_create with a configuration (NULL = spt_default_config). */
+/* spt_scene_create with a configuration (NULL = spt_default_config).
+ * SPT_ERR_LIMIT, naming the depth, when the tree built is so deep that its
+ * traversal stack (one LDS entry per lane and level, plus stack_slack) does
+ * not fit the device's shared memory per workgroup; no scene is returned. */
 spt_status spt_scene_create_cfg(const int32_t* pos_tri, const float* pos, uint64_t nvert, uint64_t ntri,
                                 const int32_t* nrm_tri, const float* nrm, uint64_t nnrm,
                                 const int32_t* tc_tri, const float* tc, uint64_t ntc,
                                 const int32_t* mat_id, const spt_config* cfg, spt_scene* out);
 
-/* Replace / read the scene's configuration (the build fields are kept as built). */
+/* Replace / read the scene's configuration (the build fields are kept as
+ * built; SPT_ERR_LIMIT if the scene's stack does not fit the device's LDS). */
 spt_status spt_scene_set_config(spt_scene scene, const spt_config* cfg);
 spt_status spt_scene_get_config(spt_scene scene, spt_config* out);
 
@@ -503,7 +507,10 @@ spt_status spt_scene_destroy(spt_scene scene);
  * spt_scene_cache_info runs all the checks without a device and
  * reports the saved stats / config / extra size (each out pointer may be
  * NULL).  spt_scene_load copies at most extra_cap bytes of extra into `extra`
- * and the full size into *extra_bytes (both may be NULL / 0). */
+ * and the full size into *extra_bytes (both may be NULL / 0).  A file whose
+ * stack_depth needs more LDS per workgroup than the current device has is
+ * refused with SPT_ERR_LIMIT (the message names the depth) before anything is
+ * uploaded; *out stays NULL. */
 spt_status spt_scene_save(spt_scene scene, const char* path, const void* extra, uint64_t extra_bytes);
 spt_status spt_scene_load(const char* path, spt_scene* out, void* extra, uint64_t extra_cap, uint64_t* extra_bytes);
 spt_status spt_scene_cache_info(const char* path, spt_scene_stats* stats, spt_config* cfg, uint64_t* extra_bytes);

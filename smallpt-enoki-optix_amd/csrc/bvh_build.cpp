@@ -54,6 +54,14 @@ struct SubTree {
     double sah = 0.0;
 };
 
+// Bin of a scaled centroid offset, clamped in float before the conversion: a
+// centroid extent in the subnormal range makes the scale, and with it f,
+// +inf, and converting a float beyond int's range is undefined (INT_MIN on
+// x86, which std::min lets through as an index).  NaN goes to bin 0.
+inline int sah_bin(float f) {
+    return f >= (float)kBins ? kBins - 1 : (f >= 0.0f ? (int)f : 0);
+}
+
 int32_t leaf_code(uint64_t first, uint64_t count) {
     return (int32_t)~(uint32_t)((first << 3) | (count - 1));
 }
@@ -101,7 +109,7 @@ struct Builder {
                 for (int i = 0; i < kBins; i++) bb[i].reset();
                 for (uint64_t i = b; i < e; i++) {
                     float f = (refs[i].c[axis] - cbox.lo[axis]) * scale;
-                    int bin = (f >= 0.0f) ? std::min((int)f, kBins - 1) : 0;
+                    int bin = sah_bin(f);
                     cnt[bin]++;
                     bb[bin].grow(refs[i].lo, refs[i].hi);
                 }
@@ -136,8 +144,7 @@ struct Builder {
                 float lo = cbox.lo[axis];
                 PrimRef* m = std::partition(refs + b, refs + e, [&](const PrimRef& r) {
                     float f = (r.c[axis] - lo) * scale;
-                    int bin = (f >= 0.0f) ? std::min((int)f, kBins - 1) : 0;
-                    return bin <= best_bin;
+                    return sah_bin(f) <= best_bin;
                 });
                 mid = (uint64_t)(m - refs);
                 split_found = mid > b && mid < e;

@@ -815,6 +815,31 @@ uint32_t bvh8_stack_entries(uint32_t depth, uint32_t slack) {
     return SPT_STACK_CAP ? std::min<uint32_t>(n, SPT_STACK_CAP) : n;
 }
 
+// The most LDS a workgroup of any trace kernel asks for with `stack_depth`
+// entries per lane (kernels.hip launch_*): the stack rows, for the wide
+// tracers the per-lane Woop and hit records behind them (Tracer8T::kExtraLds),
+// and the fused kernel's parked throughput / radiance (launch_fused_t).
+uint64_t stack_lds_bytes(uint32_t stack_depth, uint32_t width) {
+    return (uint64_t)stack_depth * kIsectBlock * sizeof(uint32_t) + (width != 2 ? 2u * kIsectBlock * 16u : 0u) +
+           kIsectBlock * 32u;
+}
+
+// Refuses a stack that does not fit the current device's LDS per workgroup,
+// before any kernel can be launched with it: the builders do not bound the
+// depth of a tree by what the device holds (the GPU builder does not bound it
+// at all), and a cache file may claim any stack_depth.
+spt_status check_stack_lds(const char* what, uint32_t stack_depth, uint32_t width) {
+    int dev = 0, cap = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || cap <= 0)
+        cap = 64 << 10;
+    const uint64_t need = stack_lds_bytes(stack_depth, width);
+    if (need > (uint64_t)cap)
+        return fail(SPT_ERR_LIMIT, "%s: a traversal stack of depth %u (BVH width %u) needs %llu B of LDS per workgroup, "
+                    "the device has %d B", what, stack_depth, width, (unsigned long long)need, cap);
+    return SPT_OK;
+}
+
 // Range checks of spt_scene_set_config / spt_scene_create_cfg.
 spt_status check_config(const spt_config& c) {
 #define CFG_RANGE(f, lo, hi)                                                                         \
@@ -889,6 +914,11 @@ spt_status create_scene_gpu(const int32_t* pos_tri, const float* pos, uint64_t n
     GpuBvh8 g;
     const int width = (int)cfg.bvh_width;
     HIP_TRY(gpu_build_bvh8(raw.tv, (uint32_t)ntri, s, &g, (int)cfg.ploc_radius, cfg.collapse == 1, width));
+    if ((us = check_stack_lds("spt_scene_create (GPU build)", bvh8_stack_entries(g.depth, cfg.stack_slack), cfg.bvh_width))) {
+        (void)hipFree(g.nodes8);
+        (void)hipFree(g.slot2tri);
+        return us;
+    }
     spt_scene_t* sc = new spt_scene_t();
     sc->cfg = cfg;
     (void)hipGetDevice(&sc->device);
@@ -1092,6 +1122,9 @@ spt_status spt_scene_create_cfg(const int32_t* pos_tri, const float* pos, uint64
         bvh = build_bvh(tv.data(), ntri);
     const std::vector<uint32_t>& slot2tri = use8 ? bvh8.slot2tri : bvh.slot2tri;
     const double t1 = now_ms();
+    const uint32_t stack_depth =
+        use8 ? bvh8_stack_entries(bvh8.depth, cfg.stack_slack) : std::max<uint32_t>(1, bvh.max_depth + 1);
+    if ((st = check_stack_lds("spt_scene_create", stack_depth, cfg.bvh_width))) return st;
 
     // Slot-ordered device arrays.
     std::vector<float4> h_tris((size_t)ntri * kTriQuads), h_snrm((size_t)ntri * 3);
@@ -1124,7 +1157,7 @@ spt_status spt_scene_create_cfg(const int32_t* pos_tri, const float* pos, uint64
     sc->cfg = cfg;
     (void)hipGetDevice(&sc->device);
     sc->ntri = ntri;
-    sc->stack_depth = use8 ? bvh8_stack_entries(bvh8.depth, cfg.stack_slack) : std::max<uint32_t>(1, bvh.max_depth + 1);
+    sc->stack_depth = stack_depth;
     const float one[3] = {1.0f, 1.0f, 1.0f};
     spt_status us = SPT_OK;
     uint32_t nslots = 0;
@@ -1269,6 +1302,11 @@ spt_status spt_scene_set_config(spt_scene sc, const spt_config* cfg) {
     spt_status st = check_config(*cfg);
     if (st) return st;
     std::lock_guard<std::mutex> lk(sc->mu);
+    // (stack_slack stays as built, below: the stack checked is the one the scene has)
+    {
+        DeviceGuard dg(sc->device);
+        if ((st = check_stack_lds("spt_scene_set_config", sc->stack_depth, sc->cfg.bvh_width))) return st;
+    }
     const spt_config old = sc->cfg;
     sc->cfg = *cfg;
     // the scene keeps the build it has
@@ -1969,6 +2007,7 @@ spt_status spt_scene_load(const char* path, spt_scene* out, void* extra, uint64_
     if (!st) st = check_config(h.cfg);
     if (st) return st;
     if ((st = ensure_device())) return st;
+    if ((st = check_stack_lds(what, h.stack_depth, h.stats.bvh_width))) return st;
     spt_scene_t* sc = new spt_scene_t();
     auto bail = [&](spt_status e) {
         sc->release();

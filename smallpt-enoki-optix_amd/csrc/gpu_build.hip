@@ -160,8 +160,11 @@ __global__ __launch_bounds__(kBlock) void nn_kernel(const float4* __restrict__ c
         if (j == (int64_t)i) continue;
         const uint32_t lj = (uint32_t)(j - b0);
         const float4 ol = slo[lj], oh = shi[lj];
-        const float a = half_area(make_float4(fminf(l.x, ol.x), fminf(l.y, ol.y), fminf(l.z, ol.z), 0.0f),
-                                  make_float4(fmaxf(h.x, oh.x), fmaxf(h.y, oh.y), fmaxf(h.z, oh.z), 0.0f));
+        float a = half_area(make_float4(fminf(l.x, ol.x), fminf(l.y, ol.y), fminf(l.z, ol.z), 0.0f),
+                            make_float4(fmaxf(h.x, oh.x), fmaxf(h.y, oh.y), fmaxf(h.z, oh.z), 0.0f));
+        // an infinite or NaN area (a non-finite coordinate, an overflowing product) still orders
+        // after every finite one: such clusters merge last, where they would never merge at all
+        if (!(a < INFINITY)) a = 3.4028234663852886e38f;  // FLT_MAX
         if (a < best) {
             best = a;
             bj = (uint32_t)j;

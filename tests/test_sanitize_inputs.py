@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import hostile
 import sptamd
 from sptamd import _lib, scenes
 
@@ -185,6 +186,13 @@ def _soups():
     yield "nonfinite", g
     m = scenes.city_synth(60_000)
     yield "city", np.asarray(m["pos"], np.float32)[np.asarray(m["pos_tri"])].reshape(-1, 9)
+    # a centroid extent in the subnormal range: the SAH bin scale is +inf (bvh_build.cpp sah_bin)
+    x = np.exp2(np.arange(-120, 120, dtype=np.float64))[:, None]
+    yield "subnormal_chain", (x * np.array([[1, 0, 0, 1.001, 0, 0, 1, 0.001, 0]])).astype(np.float32)
+    rng = np.random.default_rng(10)
+    yield "mixed_1e37", (rng.normal(size=(300, 9)) * np.exp(rng.uniform(-85, 85, size=(300, 1)))).astype(np.float32)
+    for fam in hostile.FAMILIES:
+        yield "hostile_" + fam, hostile.tri_soup(hostile.family(fam))
 
 
 @pytest.mark.parametrize("name,tv", list(_soups()), ids=lambda x: x if isinstance(x, str) else "")
