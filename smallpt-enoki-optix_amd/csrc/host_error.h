@@ -1,4 +1,4 @@
-// host_error.h — set spt_last_error() from the host-side readers (capi.cpp).
+// host_error.h — set spt_last_error() from the host-side readers (capi.cpp spt_set_error).
 #pragma once
 #include "../../include/spt.h"
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "spt_math.h"
+#include "shard_base.h"
 
 namespace spt {
 
@@ -41,39 +42,6 @@ constexpr uint32_t kShadeBlock = SPT_SHADE_BLOCK;  // shade: 8 waves, one queue 
 constexpr uint32_t kMetaDepthBits = 8;      // meta = sample << 8 | depth
 constexpr uint32_t kIsectChunk = 128;       // dynamic-share queue indices a wave takes per atomic
 constexpr uint32_t kRefillIdle = 16;        // refill a wave once this many lanes are idle
-// SPT_WORK_AUTO: pixel-major for scenes beyond the Infinity Cache, and in the
-// fused kernel for tiles of at least 16M paths (capi.cpp spt_render)
-constexpr uint64_t kPixelMajorMinSceneBytes = 256ull << 20;
-constexpr uint64_t kPixelMajorMinFusedPaths = 16ull << 20;
-// ... and in the wavefront for scenes beyond one XCD's L2 on tiles of <= 4M
-// pixels, with 24M paths in flight when the in-flight count is left at its
-// default (32M)
-constexpr uint64_t kPixelMajorMinWaveSceneBytes = 4ull << 20;
-constexpr uint64_t kPixelMajorMaxWaveTilePx = 4ull << 20;
-constexpr uint32_t kDefaultWavefrontPaths = 1u << 25;
-constexpr uint64_t kPixelMajorWavefrontPaths = 24ull << 20;
-// spt_config.drain_q8 default: a sub-wavefront's queue shorter than this many
-// 1/256ths of its persistent isect lanes goes to the drain launch
-constexpr uint32_t kDefaultDrainQ8 = 1024;
-// spt_config.fused_max_paths default: AUTO runs the fused kernel only for jobs
-// of at most 1M paths, fewer than two chip fills of lanes (config 0's 262k:
-// the wavefront's launches and streams outweigh the work, 372 vs 823 Mpaths/s)
-constexpr uint64_t kDefaultFusedMaxPaths = 1ull << 20;
-// spt_config.fit_paths default: jobs (or sample chunks, fit_chunks) of at most
-// 2^28 paths start every path at once: 21 GB of queues per working set in unit
-// mode, 34 GB with emitters (HBM is 288 GB); config 3 +3.7 % over 2^27, config
-// 2 -0.7 % (profiles/r05_exp/fit_paths_rgb_waves/)
-constexpr uint64_t kDefaultFitPaths = 1ull << 28;
-// spt_config.drain_casts default: the drain runs this many casts after a
-// sub-wavefront's last work item started, whatever its queue holds
-constexpr uint32_t kDefaultDrainCasts = 1;
-// spt_config.drain_refill_idle AUTO (0): free lanes a drain wave waits for
-// before it refills and shades — scenes with analytic spheres (tested in the
-// shade, with smallpt's mirror / glass: the pass costs several trace steps),
-// scenes whose queue is streamed (beyond the Infinity Cache), the rest
-constexpr uint32_t kDrainIdleSpheres = 56;
-constexpr uint32_t kDrainIdleStream = 40;
-constexpr uint32_t kDrainIdleCached = 24;
 
 // Path modes: what a path carries besides its ray.  The scene decides
 // (spt_render): unit = every albedo 1 and no emitters, the reference's own
@@ -246,27 +214,6 @@ SPT_HD V3 reflectance(const DeviceScene& sc, uint32_t mat, uint32_t slot, float 
     }
     if (mat >= sc.nmat) mat = 0;
     return v3(sc.albedo[mat * 3], sc.albedo[mat * 3 + 1], sc.albedo[mat * 3 + 2]);
-}
-
-// A queue filled by a sharded producer (camera_cast_kernel): survivors of
-// block b go to shard b mod kShards — the XCD the block runs on — through
-// that shard's own counter, into segment [shard_base(j), shard_base(j) +
-// count_j) of the queue.  One queue counter takes at most ~88 atomics per us
-// (MI355X_MICROARCH.md, dequeue), so a first cast of 67M paths in 262144
-// blocks on one counter waited ~3 ms for its compaction atomics; eight
-// counters (and the drain's per-XCD pools over the same segments) take
-// eight times that.  Segment j holds as many slots as shard j has threads.
-constexpr uint32_t kShards = 8;
-constexpr uint32_t kShardStride = 32;  // words between shard counters (one 128-B line each)
-SPT_HD uint32_t shard_base(uint32_t j, uint32_t items, uint32_t block) {
-    const uint32_t nb = (items + block - 1) / block;
-    uint32_t base = 0;
-    for (uint32_t i = 0; i < j; i++) {
-        if (i >= nb) break;
-        base += ((nb - 1 - i) / kShards + 1) * block;  // blocks i, i + 8, ... of `block` threads
-        if ((nb - 1) % kShards == i) base -= nb * block - items;  // the last block is short
-    }
-    return base;
 }
 
 struct RefillArgs {

@@ -30,12 +30,12 @@ rational arithmetic before it is listed.
 Rules (the name each violation carries, and where the rule comes from):
 
  Topology
-  node-range      an inner child index lies in the node array (capi.cpp:1756)
-  node-twice      every reachable node slot is reached once (capi.cpp:1731-1735)
+  node-range      an inner child index lies in the node array (scene_cache.cpp cache_check_nodes)
+  node-twice      every reachable node slot is reached once (cache_check_nodes)
   leaf-count      a wide leaf's count bits are unary, 1..3 triangles
                   (bvh_build.h:49, bvh8_build.cpp:304); a BVH2 leaf holds
                   1..kMaxLeafSize (bvh_build.h:10, :17: three count bits)
-  leaf-range      a leaf's triangle slots lie in [0, ntri) (capi.cpp:1768, :1797)
+  leaf-range      a leaf's triangle slots lie in [0, ntri) (cache_check_nodes)
   leaf-offset     a wide node's leaf offsets are contiguous in slot order from
                   tri_base (bvh_build.h:48, bvh8_build.cpp:274-306)
   tri-coverage    every triangle slot belongs to exactly one leaf
@@ -48,21 +48,21 @@ Rules (the name each violation carries, and where the rule comes from):
                   (bvh8_build.cpp:272, bvh_refit.h:167)
   stats           the node, leaf, depth and leaf-size counts of the walk equal
                   the header's scene stats.  (max_leaf of a wide tree is the
-                  format's constant 3 in the stats, capi.cpp:942 / :1173: the
+                  format's constant 3 in the stats, capi.cpp spt_scene_create_cfg: the
                   walk's largest leaf must not exceed it; BVH2: equal.)
   stack-depth     the stack the header declares holds the tree: BVH2 one entry
                   per node level, a wide tree levels - 1, at least 1
-                  (capi.cpp:1801-1806)
+                  (cache_check_nodes)
  Index arrays
-  orig2slot-perm  orig2slot is a permutation of the slots (capi.cpp:1815-1820)
+  orig2slot-perm  orig2slot is a permutation of the slots (cache_check_indices)
   orig2slot-id    float 15 of record orig2slot[i] holds i (spt_internal.h:24-34)
  Records (with a mesh)
   record          every slot's record equals tri_record_fill of the mesh's
                   current vertices of its original triangle, bit for bit
                   (spt_internal.h:25-34)
   normal          supplied vertex normals and the material id in .w of the first
-                  normal equal the mesh's, bit for bit (spt_internal.h:117,
-                  capi.cpp:1107-1113).  Geometric normals made for missing
+                  normal equal the mesh's, bit for bit (spt_internal.h:85,
+                  capi.cpp spt_scene_create_cfg).  Geometric normals made for missing
                   vertex normals are not checked here.
  Enclosure
   enclosure       for every child of every node the decoded box encloses every
@@ -109,7 +109,7 @@ from sptamd import _lib
 SECTIONS = ["nodes", "triangles", "normals", "texcoords", "orig2slot", "albedo", "emission", "spheres",
             "sphere materials", "material kinds", "texture sizes", "texels", "extra"]
 TRI_QUADS, NODE6_QUADS, NODE8_QUADS = 4, 4, 8   # spt_internal.h kTriQuads / kNode6Quads / kNode8Quads
-CACHE_VERSION = 2               # capi.cpp kCacheVersion (2: 64-B rotated triangle records)
+CACHE_VERSION = 2               # scene_cache.cpp kCacheVersion (2: 64-B rotated triangle records)
 COMPACT = 0xffffffff            # bvh_refit.h kRefitCompact
 MAX_LEAF2 = 8                   # bvh_build.h kMaxLeafSize
 REPORT_CAP = 20                 # entries listed per rule and level (the audit still fails on one)

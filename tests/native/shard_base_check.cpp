@@ -1,8 +1,10 @@
 // shard_base (spt_internal.h): the segments of a sharded queue partition the
 // producer's items exactly — segment j is as long as shard j's threads (blocks
-// b = j, j + 8, ..., the last block short).  Host-only; tests/test_host.py builds it.
-#include "spt_internal.h"
+// b = j, j + 8, ..., the last block short).  Host-only; tests/test_host.py builds it
+// with the host compiler and an empty SPT_HD.
+#include "shard_base.h"
 #include <cstdio>
+#include <initializer_list>
 int main() {
     using namespace spt;
     long bad = 0, cases = 0;

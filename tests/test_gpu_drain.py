@@ -1,5 +1,5 @@
-"""The wavefront's drain (kernels.hip render_fused_kernel<kDrain>, capi.cpp
-spt_render_async): once a sub-wavefront's last work item has started, a queue
+"""The wavefront's drain (kernels.hip render_fused_kernel<kDrain>, render.cpp
+render_enqueue): once a sub-wavefront's last work item has started, a queue
 shorter than drain_q8/256 of its isect lanes — or any queue drain_casts casts
 later — is finished by one launch whose lanes continue each path in registers.
 Every combination must give the oracle's bits and the device-counted work:
@@ -252,7 +252,7 @@ def test_fit_bytes_shrinks_fit(mesh, mode, monkeypatch):
 @pytest.mark.parametrize("mode", ["unit", "emit_spheres"])
 @pytest.mark.parametrize("nth", [1, 5, 8])
 def test_oom_retry_frees_and_halves(mesh, mode, nth, monkeypatch):
-    """The fit whose working-set allocation fails anyway (capi.cpp retry_fit,
+    """The fit whose working-set allocation fails anyway (render.cpp plan_and_allocate,
     ADVICE / VERDICT r5): spt_debug_fail_workspace_alloc makes the nth device
     allocation of a fresh working set fail once — inside sub-wavefront 0's
     queues, inside sub-wavefront 1's, the film chunk (two sub-wavefronts: qa,

@@ -3,7 +3,7 @@ queued with spt_render_async capture the scene's device arrays when they are
 queued; spt_scene_set_albedo / set_emission / set_texture / set_spheres /
 set_material_kinds free and replace those arrays.  The mutators wait for every
 queued render of both working sets and for the last public call on every
-stream (capi.cpp quiesce_scene) before they free anything, so each render
+stream (render.cpp quiesce_scene) before they free anything, so each render
 equals the oracle for the materials it was queued with, and a ray cast queued
 before set_spheres still sees the old spheres."""
 import numpy as np
