@@ -768,6 +768,87 @@ size_t spt_denoise_var_scratch_bytes(uint32_t width, uint32_t height);
 spt_status spt_denoise_var(const spt_denoise_var_params* p, const float* color, const float* variance,
                            const spt_aov* guides, float* out, float* variance_out, void* scratch, void* stream);
 
+/* Adaptive sampling (a build addition): which pixels of an accumulation still
+ * need samples, as an ascending list, and a pass of spt_render_accum over a
+ * list of pixels instead of the whole tile.
+ *
+ * Selection.  count[p] is the number of samples pixel p's sums hold.  Pixel p
+ * is ACTIVE for a pass starting at n = sample_base iff
+ *   n == 0   (every pixel; count, sum and sum_sq are not read), or
+ *   count[p] == n && (n < min_spp || (n < max_spp && !converged(p))),
+ * with, every operation rounded to f32 and nothing contracted (the arithmetic
+ * of spt_render_accum's variance), per channel c
+ *   m_c = sum_c / (float)n,   q_c = sum_sq_c / (float)n,
+ *   var_c = n < 2 ? 0 : fmaxf(q_c - m_c * m_c, 0) / (float)(n - 1),
+ * and
+ *   v = (var_r + var_g) + var_b,   m = (m_r + m_g) + m_b,
+ *   t = tolerance * fmaxf(m, floor),   converged = v <= t * t.
+ * tolerance bounds the relative standard error of the pixel mean (channels
+ * summed); floor is the least mean it is relative to, so dark pixels stop.
+ * The two fmaxf here return a NaN first operand as it is (C's would hide it
+ * behind the 0 or the floor; on numbers they are C's), so a NaN anywhere makes
+ * the comparison false: such a pixel is sampled up to max_spp.  A pixel whose count is not n (it left an earlier pass's list) is
+ * never active again, so count is the length of a prefix of the pixel's
+ * samples.  Stopping on a rule computed from the samples themselves is biased:
+ * a pixel whose first samples happen to agree stops early; min_spp is the
+ * guard. */
+typedef struct spt_adapt_params {
+    uint32_t min_spp, max_spp;   /* every pixel gets at least min_spp, none more than max_spp */
+    float tolerance;             /* relative standard error of the pixel mean, summed over channels */
+    float floor;                 /* the mean it is relative to is at least this (dark pixels) */
+    uint32_t reserved[2];        /* 0 */
+} spt_adapt_params;
+
+/* min_spp 8, max_spp 1024, tolerance 0.05, floor 0.03: chosen on the CPU
+ * restatement (tests/adaptive_ref.py). */
+void spt_default_adapt_params(spt_adapt_params* p);
+
+/* Bytes of device scratch spt_adapt_select needs for npix pixels: one 64-bit
+ * ballot per 64 pixels and one 32-bit total per 256 pixels plus one, rounded up
+ * to 16:  (8 ceil(npix / 64) + 4 (ceil(npix / 256) + 1) + 15) & ~15. */
+size_t spt_adapt_select_scratch_bytes(uint32_t npix);
+
+/* list[0 .. *n_active) = the active pixels of [0, npix) in ascending order,
+ * the same list on every run (an ordered compaction: ballots, block totals, a
+ * scan of the totals; no atomic append).  sum, sum_sq: spt_accum's planes
+ * (3 x npix floats), count: npix words, list: npix words, scratch:
+ * spt_adapt_select_scratch_bytes(npix) bytes, all on the device and 4-byte
+ * aligned; list[*n_active ..) is left as it was.  n_active is a host pointer:
+ * the call queues its launches on `stream`, waits for them and returns the
+ * count.  It has no scene and never allocates.  Before any device work:
+ * SPT_ERR_INVALID for a NULL p, list, n_active or scratch, NULL sum, sum_sq or
+ * count with sample_base > 0, reserved != 0, min_spp > max_spp, a tolerance or
+ * floor that is negative or not finite; SPT_ERR_LIMIT for sample_base >= 2^24
+ * or npix >= 2^31.  npix = 0 gives *n_active = 0. */
+spt_status spt_adapt_select(const spt_adapt_params* p, uint32_t npix, uint32_t sample_base, const float* sum,
+                            const float* sum_sq, const uint32_t* count, uint32_t* list, uint32_t* n_active,
+                            void* scratch, void* stream);
+
+/* A pass over listed pixels: for every tile pixel in pixels[0 .. n) exactly
+ * what spt_render_accum does for that pixel, bit for bit — samples
+ * [sample_base, sample_base + spp) onto sum / sum_sq, then film and variance —
+ * in every pipeline, work order, film chunking and lockstep_first setting
+ * (a listed pixel's sample is its sample in a full pass: the same random
+ * numbers, keyed by the pixel, not by its place in the list).  Every element
+ * of the four planes and of count that belongs to an unlisted pixel is left
+ * untouched.  count, when not NULL, gets sample_base + spp for listed pixels.
+ * A list of every tile pixel is spt_render_accum, stats included.  n == 0 is
+ * SPT_OK: nothing is queued, the stats are zero.  Stats describe the pass:
+ * paths = n x params->spp.  The call is synchronous: a kernel first checks
+ * that the list is strictly ascending and in range (SPT_ERR_INVALID otherwise,
+ * nothing written), then the pass runs and is waited for.  Besides
+ * spt_render_accum's errors: SPT_ERR_INVALID for a NULL list or pixels (n > 0),
+ * reserved != 0, n > tile pixels, or pixels / count overlapping each other or
+ * one of the four planes. */
+typedef struct spt_pixel_list {
+    const uint32_t* pixels;  /* device: n tile pixels, strictly ascending, each < tile pixels */
+    uint32_t n;
+    uint32_t reserved;       /* 0 */
+    uint32_t* count;         /* device, in/out, tile pixels, may be NULL: set to sample_base + spp for listed pixels */
+} spt_pixel_list;
+spt_status spt_render_accum_list(spt_scene scene, const spt_render_params* params, const spt_accum* acc,
+                                 const spt_pixel_list* list, spt_render_stats* stats, void* stream);
+
 /* The isect kernel's busy time across queued renders (a build addition, for the
  * roofline: renders queued back to back overlap, so per-render busy times do
  * not add up).  After _begin, every SPT_FLAG_TIMING render collected by

@@ -1075,4 +1075,61 @@ spt_status spt_denoise_var(const spt_denoise_var_params* pp, const float* color,
     return SPT_OK;
 }
 
+void spt_default_adapt_params(spt_adapt_params* p) {
+    if (!p) return;
+    // chosen on tests/adaptive_ref.py's schedules
+    p->min_spp = 8;
+    p->max_spp = 1024;
+    p->tolerance = 0.05f;
+    p->floor = 0.03f;
+    p->reserved[0] = p->reserved[1] = 0;
+}
+
+size_t spt_adapt_select_scratch_bytes(uint32_t npix) {
+    const size_t waves = ((size_t)npix + 63) / 64, blocks = ((size_t)npix + kAdaptBlock - 1) / kAdaptBlock;
+    return (8 * waves + 4 * (blocks + 1) + 15) & ~(size_t)15;
+}
+
+spt_status spt_adapt_select(const spt_adapt_params* pp, uint32_t npix, uint32_t sample_base, const float* sum,
+                            const float* sum_sq, const uint32_t* count, uint32_t* list, uint32_t* n_active,
+                            void* scratch, void* stream_) {
+    if (!pp || !list || !n_active || !scratch)
+        return fail(SPT_ERR_INVALID, "spt_adapt_select: NULL params / list / n_active / scratch");
+    const spt_adapt_params& p = *pp;
+    if (sample_base > 0 && (!sum || !sum_sq || !count))
+        return fail(SPT_ERR_INVALID, "spt_adapt_select: NULL sum / sum_sq / count with sample_base > 0");
+    if (p.reserved[0] != 0 || p.reserved[1] != 0) return fail(SPT_ERR_INVALID, "spt_adapt_select: reserved must be 0");
+    if (p.min_spp > p.max_spp)
+        return fail(SPT_ERR_INVALID, "spt_adapt_select: min_spp %u > max_spp %u", p.min_spp, p.max_spp);
+    if (!(p.tolerance >= 0.0f) || !std::isfinite(p.tolerance) || !(p.floor >= 0.0f) || !std::isfinite(p.floor))
+        return fail(SPT_ERR_INVALID, "spt_adapt_select: tolerance and floor must be finite and >= 0");
+    if (((uintptr_t)list | (uintptr_t)scratch | (uintptr_t)sum | (uintptr_t)sum_sq | (uintptr_t)count) & 3u)
+        return fail(SPT_ERR_INVALID, "spt_adapt_select: buffers must be 4-byte aligned");
+    if (sample_base >= (1u << 24)) return fail(SPT_ERR_LIMIT, "spt_adapt_select: sample_base must be < 2^24");
+    if (npix >= (1u << 31)) return fail(SPT_ERR_LIMIT, "spt_adapt_select: too many pixels");
+    *n_active = 0;
+    if (npix == 0) return SPT_OK;
+    const hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t blocks = (npix + kAdaptBlock - 1) / kAdaptBlock;
+    AdaptArgs a{};
+    a.sum = sum; a.sum_sq = sum_sq; a.count = count;
+    a.list = list;
+    a.masks = (uint32_t*)scratch;
+    a.totals = a.masks + 2 * (size_t)((npix + 63u) / 64u);
+    a.npix = npix; a.n = sample_base;
+    a.min_spp = p.min_spp; a.max_spp = p.max_spp;
+    a.tolerance = p.tolerance; a.floor = p.floor;
+    HIP_TRY(launch_adapt_select(a, stream));
+    if (sample_base == 0) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        *n_active = npix;
+        return SPT_OK;
+    }
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, a.totals + blocks, sizeof(n), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *n_active = n;
+    return SPT_OK;
+}
+
 }  // extern "C"

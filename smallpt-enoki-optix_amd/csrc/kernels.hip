@@ -699,12 +699,20 @@ __device__ __forceinline__ TraceHit trace(const DeviceScene& sc, V3 o, V3 d, flo
 __device__ __forceinline__ void camera_ray(const Camera& cam, Pcg32& rng, uint32_t order, uint32_t x, uint32_t y,
                                            V3& o, V3& d);
 
-// A new camera path for work item w (refill_kernel's arithmetic): its ray,
-// tile pixel p and meta (sample << 8, cast 0).
+// A new camera path for work item w (refill_kernel's arithmetic, kList
+// included): its ray, tile pixel p and meta (sample << 8, cast 0).
+template <bool kList = false>
 __device__ __forceinline__ void start_path(const RefillArgs& r, uint64_t w, V3& o, V3& d, uint32_t& p, uint32_t& meta) {
     uint32_t s, q, lx, ly;
-    work_item((uint32_t)(w - (uint64_t)r.chunk_s0 * r.P), r.chunk_s0, r.chunk_ns, r.P, r.work_order != 0, s, q);
-    work_pixel(q, r.W, r.P, r.pixel_block, lx, ly);
+    const uint32_t npx = kList ? r.list_n : r.P;  // pixels that take samples
+    work_item((uint32_t)(w - (uint64_t)r.chunk_s0 * npx), r.chunk_s0, r.chunk_ns, npx, r.work_order != 0, s, q);
+    if constexpr (kList) {
+        const uint32_t lp = r.list[q];
+        ly = udiv(lp, r.W);
+        lx = lp - ly * r.W;
+    } else {
+        work_pixel(q, r.W, r.P, r.pixel_block, lx, ly);
+    }
     p = ly * r.W + lx;
     const uint32_t gy = tile_global_row(ly, r.tile_index, r.tile_count, r.rows_per_group);
     const uint32_t gpix = gy * r.W + lx;                    // main.cpp:379-382
@@ -959,7 +967,11 @@ __device__ __forceinline__ Pcg32 path_rng(uint32_t gpix, const PcgJump& js, cons
 // sizes it before it knows how many paths ended): config 1 +0.9 %, config 2
 // +1.8 % (profiles/r03_tune/knob_sweep.log).
 constexpr uint32_t kRefillMaxBlocks = 4096;
-template <int kMode, bool kNt = false>
+// kList (spt_render_accum_list): work item w is sample w / list_n of the
+// w % list_n-th listed pixel; the path carries that tile pixel, so everything
+// after the camera ray is a full pass's (separate instances: the lookup stays
+// out of the others' loop).
+template <int kMode, bool kNt = false, bool kList = false>
 __global__ __launch_bounds__(256) void refill_kernel(RefillArgs a) {
     uint32_t surv = 0;
     if (a.surv_shards)
@@ -989,9 +1001,16 @@ __global__ __launch_bounds__(256) void refill_kernel(RefillArgs a) {
     if (a.book_only) return;
     for (uint32_t j = i; j < total; j += gridDim.x * 256u) {
         uint32_t s, q, lx, ly;
-        work_item((uint32_t)(cur + j - (uint64_t)a.chunk_s0 * a.P), a.chunk_s0, a.chunk_ns, a.P, a.work_order != 0, s,
+        const uint32_t npx = kList ? a.list_n : a.P;  // pixels that take samples
+        work_item((uint32_t)(cur + j - (uint64_t)a.chunk_s0 * npx), a.chunk_s0, a.chunk_ns, npx, a.work_order != 0, s,
                   q);
-        work_pixel(q, a.W, a.P, a.pixel_block, lx, ly);
+        if constexpr (kList) {
+            const uint32_t lp = a.list[q];
+            ly = udiv(lp, a.W);
+            lx = lp - ly * a.W;
+        } else {
+            work_pixel(q, a.W, a.P, a.pixel_block, lx, ly);
+        }
         const uint32_t p = ly * a.W + lx;
         const uint32_t gy = tile_global_row(ly, a.tile_index, a.tile_count, a.rows_per_group);
         const uint32_t gpix = gy * a.W + lx;                    // main.cpp:379-382
@@ -1243,7 +1262,7 @@ struct CamSrc {  // the path in registers: its first cast, just traced
     __device__ __forceinline__ float4 q0() const { return make_float4(1.0f, 1.0f, 1.0f, 0.0f); }  // main.cpp:391
     __device__ __forceinline__ float2 rad() const { return make_float2(0.0f, 0.0f); }
 };
-template <typename Tr, int kMode, bool kSpt, bool kNt>
+template <typename Tr, int kMode, bool kSpt, bool kNt, bool kList = false>
 __global__ __launch_bounds__(kIsectBlock) __attribute__((amdgpu_waves_per_eu(Tr::kMinWaves, 8)))
 void camera_cast_kernel(CameraCastArgs a) {
     extern __shared__ uint32_t lds_stack[];
@@ -1258,7 +1277,7 @@ void camera_cast_kernel(CameraCastArgs a) {
     c.h.t = kRayTmax;
     c.h.u = c.h.v = 0.0f;
     if (valid) {
-        start_path(a.r, a.r.cursor_init + i, c.o, c.d, c.pix, c.meta);
+        start_path<kList>(a.r, a.r.cursor_init + i, c.o, c.d, c.pix, c.meta);
         NoStats st;
         Tr tr;
         // any-hit for the last cast unless emitters need the surface (isect_queue_kernel)
@@ -1371,7 +1390,10 @@ __global__ __launch_bounds__(kIsectBlock) void aov_kernel(AovArgs a) {
 // falls below drain_below the per-cast launches (each ending in the latency
 // tail of its slowest ray) stop and one launch finishes every path.  Same
 // arithmetic, same film writes, so the same bits as the queue kernels.
-template <typename Tr, int kMode, bool kDrain = false, bool kNt = false>
+//
+// kList (spt_render_accum_list, never with kDrain): a new path's work item runs
+// over the list_n listed pixels and its pixel is list[q] (refill_kernel).
+template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false>
 __global__ __launch_bounds__(kIsectBlock)
 __attribute__((amdgpu_waves_per_eu(kDrain && kMode == kModeUnit ? (kNt ? SPT_DRAIN_WAVES_NT : SPT_DRAIN_WAVES)
                                    : kDrain ? SPT_DRAIN_WAVES_RGB : SPT_FUSED_WAVES, 8)))
@@ -1612,7 +1634,9 @@ void render_fused_kernel(FusedArgs a) {
                     need_init = true;
                 } else if (!kDrain && !busy && !pending && rank < take) {
                     uint32_t sample;
-                    work_item(pool + rank, a.sample0, a.pm_ns, a.P, a.pm_ns != 0, sample, pix);  // work0 = sample0 * P
+                    work_item(pool + rank, a.sample0, a.pm_ns, kList ? a.list_n : a.P, a.pm_ns != 0, sample,
+                              pix);  // work0 = sample0 * P
+                    if constexpr (kList) pix = a.list[pix];
                     const uint32_t lx = pix % a.W, ly = pix / a.W;  // scanline (pixel blocks: refill_kernel only)
                     const uint32_t gy = tile_global_row(ly, a.tile_index, a.tile_count, a.rows_per_group);
                     const uint32_t gpix = gy * a.W + lx;           // main.cpp:379-382
@@ -1868,6 +1892,86 @@ __global__ __launch_bounds__(256) void resolve_flags_accum_kernel(const uint8_t*
     }
 }
 
+// spt_render_accum_list's resolves: lane j is tile pixel pixels[j], with
+// resolve_accum_kernel's reads, sample order, arithmetic and accum_finish; the
+// film chunk is the tile's (slots indexed by the tile pixel), only this pixel's
+// elements of the planes and of count are written, and the slots counted as
+// unwritten are the listed pixels'.
+__global__ __launch_bounds__(256) void resolve_accum_list_kernel(const float* __restrict__ sfilm, ResolveListArgs l) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= l.n) return;
+    const ResolveAccumArgs& a = l.r;
+    const uint32_t p = l.pixels[j];
+    const size_t P = a.P;
+    const bool sq = a.sum_sq != nullptr;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, q0 = 0.0f, q1 = 0.0f, q2 = 0.0f;
+    if (!a.from_zero) {
+        s0 = a.sum[p]; s1 = a.sum[P + p]; s2 = a.sum[2 * P + p];
+        if (sq) { q0 = a.sum_sq[p]; q1 = a.sum_sq[P + p]; q2 = a.sum_sq[2 * P + p]; }
+    }
+    uint32_t lost = 0;
+    for (uint32_t s = 0; s < a.nsamples; s++) {
+        size_t cs;
+        const float* x = film_rgb(const_cast<float*>(sfilm), s, p, a.P, a.nsamples, a.order, cs);
+        const float x0 = x[0], x1 = x[cs], x2 = x[2 * cs];
+        if (f2u(x0) == kFilmSentinel) lost++;
+        s0 = s0 + x0; s1 = s1 + x1; s2 = s2 + x2;
+        q0 = q0 + x0 * x0; q1 = q1 + x1 * x1; q2 = q2 + x2 * x2;
+    }
+    a.sum[p] = s0; a.sum[P + p] = s1; a.sum[2 * P + p] = s2;
+    if (sq) { a.sum_sq[p] = q0; a.sum_sq[P + p] = q1; a.sum_sq[2 * P + p] = q2; }
+    if (a.last) {
+        accum_finish(a, p, s0, q0);
+        accum_finish(a, P + p, s1, q1);
+        accum_finish(a, 2 * P + p, s2, q2);
+        if (l.count) l.count[p] = a.n_total;
+    }
+    if (lost) atomicAdd(a.unwritten, (unsigned long long)lost);
+}
+
+// ... and resolve_flags_accum_kernel's (unit mode; the byte loop serves both
+// film orders: a sparse list has no run of pixels to vectorise over)
+__global__ __launch_bounds__(256) void resolve_flags_accum_list_kernel(const uint8_t* __restrict__ sflag,
+                                                                       ResolveListArgs l) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= l.n) return;
+    const ResolveAccumArgs& a = l.r;
+    const uint32_t p = l.pixels[j];
+    const uint32_t nsamples = a.nsamples;
+    uint32_t k = 0, lost = 0;
+    for (uint32_t s = 0; s < nsamples; s++) {
+        const uint32_t f = sflag[film_slot(s, p, a.P, nsamples, a.order)];
+        lost += f == kFlagSentinel ? 1u : 0u;
+        k += f == 1u ? 1u : 0u;
+    }
+    if (lost) atomicAdd(a.unwritten, (unsigned long long)lost);
+    const float env[3] = {a.env_r, a.env_g, a.env_b};
+    for (uint32_t c = 0; c < 3; c++) {
+        const size_t i = (size_t)c * a.P + p;
+        const float e = env[c], ee = e * e;
+        float sum = a.from_zero ? 0.0f : a.sum[i];
+        float sq = a.from_zero || !a.sum_sq ? 0.0f : a.sum_sq[i];
+        for (uint32_t t = 0; t < k; t++) {
+            sum = sum + e;
+            sq = sq + ee;
+        }
+        a.sum[i] = sum;
+        if (a.sum_sq) a.sum_sq[i] = sq;
+        if (a.last) accum_finish(a, i, sum, sq);
+    }
+    if (a.last && l.count) l.count[p] = a.n_total;
+}
+
+// spt_render_accum_list's check: *bad = 1 unless the list is strictly
+// ascending and in range (every lane that finds a fault stores the same 1).
+__global__ __launch_bounds__(256) void list_validate_kernel(const uint32_t* __restrict__ pixels, uint32_t n, uint32_t P,
+                                                            uint32_t* __restrict__ bad) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t p = pixels[j];
+    if (p >= P || (j > 0 && pixels[j - 1] >= p)) *bad = 1u;
+}
+
 // optix_backend.h:462-486 + main.cpp:325 for the public ABI.
 __global__ __launch_bounds__(256) void hit_info_kernel(HitInfoArgs a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -2025,8 +2129,11 @@ hipError_t launch_isect_lockstep(const IsectQueueArgs& a, uint32_t grid_items, h
 template <typename Tr, int kMode, bool kSpt, bool kNt>
 static hipError_t launch_camera_cast_t(const CameraCastArgs& a, hipStream_t s) {
     const size_t lds = (size_t)a.s.sc.stack_depth * Tr::kStackWords * kIsectBlock * sizeof(uint32_t) + Tr::kExtraLds;
-    hipLaunchKernelGGL((camera_cast_kernel<Tr, kMode, kSpt, kNt>), dim3(blocks_for(a.n, kIsectBlock)),
-                       dim3(kIsectBlock), lds, s, a);
+    const dim3 g(blocks_for(a.n, kIsectBlock)), b(kIsectBlock);
+    if (a.r.list)  // spt_render_accum_list
+        hipLaunchKernelGGL((camera_cast_kernel<Tr, kMode, kSpt, kNt, true>), g, b, lds, s, a);
+    else
+        hipLaunchKernelGGL((camera_cast_kernel<Tr, kMode, kSpt, kNt>), g, b, lds, s, a);
     return hipGetLastError();
 }
 
@@ -2138,7 +2245,7 @@ hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipSt
     return hipGetLastError();
 }
 
-template <typename Tr, int kMode, bool kDrain = false, bool kNt = false>
+template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false>
 static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
     static thread_local size_t cached_lds = 0;
     static thread_local uint32_t cached = 0;
@@ -2150,7 +2257,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     (void)hipGetDevice(&dev);
     if (!cached || cached_lds != lds || cached_dev != dev) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt>,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList>,
                                                          kIsectBlock, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -2163,7 +2270,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     // (the drain's grid cannot follow its count, which is on the device)
     const uint32_t blocks = kDrain ? scaled : min(scaled, blocks_for(a.count > 0 ? a.count : 1, kIsectBlock));
     if (lanes_out) *lanes_out = blocks * kIsectBlock;
-    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt>), dim3(blocks), dim3(kIsectBlock), lds, s, a);
+    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList>), dim3(blocks), dim3(kIsectBlock), lds, s, a);
     return hipGetLastError();
 }
 
@@ -2239,7 +2346,19 @@ hipError_t launch_drain(const FusedArgs& a, int mode, hipStream_t s) {
     return launch_drain_m<kModeUnit, false>(a, s);
 }
 
+template <typename Tr>
+static hipError_t launch_fused_list(const FusedArgs& a, int mode, hipStream_t s, uint32_t* lanes_out) {
+    if (mode == kModeEmit) return launch_fused_t<Tr, kModeEmit, false, false, true>(a, s, lanes_out);
+    if (mode == kModeAlbedo) return launch_fused_t<Tr, kModeAlbedo, false, false, true>(a, s, lanes_out);
+    return launch_fused_t<Tr, kModeUnit, false, false, true>(a, s, lanes_out);
+}
+
 hipError_t launch_fused(const FusedArgs& a, int mode, hipStream_t s, uint32_t* lanes_out) {
+    if (a.list) {  // spt_render_accum_list
+        if (a.sc.nodes8 && a.sc.node6) return launch_fused_list<Tracer6F>(a, mode, s, lanes_out);
+        if (a.sc.nodes8) return launch_fused_list<Tracer8F>(a, mode, s, lanes_out);
+        return launch_fused_list<Tracer>(a, mode, s, lanes_out);
+    }
     if (a.sc.nodes8 && a.sc.node6) {
         if (mode == kModeEmit) return launch_fused_t<Tracer6F, kModeEmit>(a, s, lanes_out);
         if (mode == kModeAlbedo) return launch_fused_t<Tracer6F, kModeAlbedo>(a, s, lanes_out);
@@ -2257,6 +2376,16 @@ hipError_t launch_fused(const FusedArgs& a, int mode, hipStream_t s, uint32_t* l
 
 hipError_t launch_refill(const RefillArgs& a, uint32_t grid_items, hipStream_t s) {
     const dim3 g(std::min<uint32_t>(blocks_for(grid_items > 0 ? grid_items : 1, 256), kRefillMaxBlocks)), b(256);
+    if (a.list) {  // spt_render_accum_list
+        if (a.nt) {
+            if (a.mode == kModeEmit) hipLaunchKernelGGL((refill_kernel<kModeEmit, true, true>), g, b, 0, s, a);
+            else if (a.mode == kModeAlbedo) hipLaunchKernelGGL((refill_kernel<kModeAlbedo, true, true>), g, b, 0, s, a);
+            else hipLaunchKernelGGL((refill_kernel<kModeUnit, true, true>), g, b, 0, s, a);
+        } else if (a.mode == kModeEmit) hipLaunchKernelGGL((refill_kernel<kModeEmit, false, true>), g, b, 0, s, a);
+        else if (a.mode == kModeAlbedo) hipLaunchKernelGGL((refill_kernel<kModeAlbedo, false, true>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((refill_kernel<kModeUnit, false, true>), g, b, 0, s, a);
+        return hipGetLastError();
+    }
     if (a.nt) {
         if (a.mode == kModeEmit) hipLaunchKernelGGL((refill_kernel<kModeEmit, true>), g, b, 0, s, a);
         else if (a.mode == kModeAlbedo) hipLaunchKernelGGL((refill_kernel<kModeAlbedo, true>), g, b, 0, s, a);
@@ -2294,6 +2423,24 @@ hipError_t launch_resolve_accum(const float* sfilm, const ResolveAccumArgs& a, h
 hipError_t launch_resolve_flags_accum(const uint8_t* sflag, const ResolveAccumArgs& a, hipStream_t s) {
     if (a.P == 0) return hipSuccess;
     hipLaunchKernelGGL(resolve_flags_accum_kernel, dim3(blocks_for(a.P, 256)), dim3(256), 0, s, sflag, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_accum_list(const float* sfilm, const ResolveListArgs& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(resolve_accum_list_kernel, dim3(blocks_for(a.n, 256)), dim3(256), 0, s, sfilm, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_flags_accum_list(const uint8_t* sflag, const ResolveListArgs& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(resolve_flags_accum_list_kernel, dim3(blocks_for(a.n, 256)), dim3(256), 0, s, sflag, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_list_validate(const uint32_t* pixels, uint32_t n, uint32_t P, uint32_t* bad, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(list_validate_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, pixels, n, P, bad);
     return hipGetLastError();
 }
 

@@ -217,6 +217,12 @@ int main(int argc, char** argv) {
     bool do_denoise = false, do_denoise_var = false;
     std::string variance_out;
     int passes = 0;  // 0: one spt_render
+    // --adaptive TOL: passes of -s, 2 -s, 4 -s, ... samples (each pass as long as
+    // all before it) over the pixels spt_adapt_select still finds unconverged
+    bool adaptive = false;
+    spt_adapt_params ap;
+    spt_default_adapt_params(&ap);
+    std::string spp_map_out;
     int denoise_iters = -1;  // -1: spt_default_denoise_params
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
@@ -249,6 +255,10 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-var") do_denoise_var = true;
         else if (a == "--passes") passes = std::atoi(next());
         else if (a == "--variance") variance_out = next();
+        else if (a == "--adaptive") { adaptive = true; ap.tolerance = (float)std::atof(next()); }
+        else if (a == "--min-spp") ap.min_spp = (uint32_t)std::atoi(next());
+        else if (a == "--max-spp") ap.max_spp = (uint32_t)std::atoi(next());
+        else if (a == "--spp-map") spp_map_out = next();
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
     }
@@ -263,6 +273,18 @@ int main(int argc, char** argv) {
         std::cerr << "--passes takes N >= 1; --passes / --variance render on one device: not with --gpus above 1\n";
         return 2;
     }
+    if (adaptive && (ngpu > 1 || passes > 0)) {
+        std::cerr << "--adaptive renders on one device and sets its own passes: not with --gpus above 1 or --passes\n";
+        return 2;
+    }
+    if (!adaptive && !spp_map_out.empty()) {
+        std::cerr << "--spp-map goes with --adaptive\n";
+        return 2;
+    }
+    if (adaptive && (ap.min_spp > ap.max_spp || !(ap.tolerance >= 0.0f) || ap.max_spp >= (1u << 24))) {
+        std::cerr << "--adaptive takes TOL >= 0, --min-spp <= --max-spp < 2^24\n";
+        return 2;
+    }
     if (do_denoise && do_denoise_var) {
         std::cerr << "--denoise and --denoise-var: choose one\n";
         return 2;
@@ -272,8 +294,8 @@ int main(int argc, char** argv) {
         return 2;
     }
     // the accumulating path: asked for, or needed for the variance
-    const bool accum = passes > 0 || !variance_out.empty() || do_denoise_var;
-    const bool moments = !variance_out.empty() || do_denoise_var;
+    const bool accum = passes > 0 || !variance_out.empty() || do_denoise_var || adaptive;
+    const bool moments = !variance_out.empty() || do_denoise_var || adaptive;
     if (passes == 0) passes = 1;
     if ((want_aov || accum) && ngpu == 1) ngpu = 0;  // one tile: the single-device path below (the same image)
     try {
@@ -327,7 +349,7 @@ int main(int argc, char** argv) {
             spt_render_params whole = p;
             auto t0 = clock_t_::now();
             if (accum) {
-                if ((uint64_t)p.spp * (uint64_t)passes >= (1ull << 24))
+                if (!adaptive && (uint64_t)p.spp * (uint64_t)passes >= (1ull << 24))
                     throw std::runtime_error("--passes x -s must stay below 2^24 samples");
                 whole.spp = p.spp * (uint32_t)passes;
                 sums.reset(new spt::DeviceFloats(3 * npx));
@@ -340,12 +362,53 @@ int main(int argc, char** argv) {
                 acc.sum_sq = moments ? sums_sq->get() : nullptr;
                 acc.film = film;
                 acc.variance = moments ? variance->get() : nullptr;
-                for (int k = 0; k < passes; k++) {
-                    spt_render_stats ps{};
-                    acc.sample_base = (uint32_t)k * p.spp;
-                    scene.render_accum(p, acc, &ps);
-                    st.paths += ps.paths;
-                    st.ray_casts += ps.ray_casts;
+                if (adaptive) {
+                    // per-pixel sample counts, the active list and the selection's scratch
+                    spt::DeviceFloats count(npx), list(npx);
+                    spt::DeviceFloats scratch(spt_adapt_select_scratch_bytes((uint32_t)npx) / sizeof(float));
+                    hip_check(hipMemset(count.get(), 0, sizeof(uint32_t) * npx), "hipMemset count");
+                    spt_pixel_list pl{};
+                    pl.pixels = (const uint32_t*)list.get();
+                    pl.count = (uint32_t*)count.get();
+                    spt_render_params q = p;
+                    uint32_t base = 0, npass = 0;
+                    uint64_t next = p.spp;
+                    for (;; npass++, next *= 2) {
+                        // passes grow: -s, 2 -s, 4 -s, ... samples, the last cut at max_spp
+                        if (base >= ap.max_spp) break;
+                        q.spp = (uint32_t)std::min<uint64_t>(next, ap.max_spp - base);
+                        pl.n = spt::adapt_select(ap, (uint32_t)npx, base, acc.sum, acc.sum_sq, pl.count,
+                                                 (uint32_t*)list.get(), scratch.get());
+                        if (pl.n == 0) break;
+                        spt_render_stats ps{};
+                        acc.sample_base = base;
+                        scene.render_accum_list(q, acc, pl, &ps);
+                        st.paths += ps.paths;
+                        st.ray_casts += ps.ray_casts;
+                        base += q.spp;
+                    }
+                    whole.spp = std::max<uint32_t>(base, 1);
+                    std::cout << "adaptive passes " << npass << " samples up to " << base << " total paths " << st.paths
+                              << std::endl;
+                    if (!spp_map_out.empty()) {
+                        const std::vector<float> c = count.to_host();  // uint32 bits
+                        std::vector<float> f(npx);
+                        for (size_t i = 0; i < npx; i++) {
+                            uint32_t u;
+                            std::memcpy(&u, &c[i], sizeof(u));
+                            f[i] = (float)u;
+                        }
+                        spt::check(spt_pfm_write(spp_map_out.c_str(), f.data(), f.data(), f.data(), p.width, p.height),
+                                   "spt_pfm_write");
+                    }
+                } else {
+                    for (int k = 0; k < passes; k++) {
+                        spt_render_stats ps{};
+                        acc.sample_base = (uint32_t)k * p.spp;
+                        scene.render_accum(p, acc, &ps);
+                        st.paths += ps.paths;
+                        st.ray_casts += ps.ray_casts;
+                    }
                 }
             } else {
                 scene.render(p, film, &st);    // main.cpp:385-429

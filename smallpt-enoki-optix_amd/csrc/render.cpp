@@ -80,6 +80,7 @@ struct RenderSlot {
     double wall0 = 0.0;
     uint64_t ticket = 0;
     bool pending = false;                       // queued, not yet collected by spt_render_wait
+    bool empty = false;                         // nothing was queued (an empty tile, an empty pixel list)
 };
 
 // One sub-wavefront: its own double-buffered path queue, hit records and
@@ -221,6 +222,9 @@ struct spt::Workspace {
     RenderSlot slots[kRenderSlots];     // renders queued by spt_render_async (ticket % kRenderSlots)
     uint64_t next_ticket = 1;
     hipEvent_t epoch = nullptr;         // the first timed render's time origin: isect_begin/end_ms count from it
+    // spt_render_accum_list: the list check's verdict on the device and its pinned readback
+    uint32_t* list_bad = nullptr;
+    uint32_t* list_bad_host = nullptr;
     // spt_scene_isect_busy_begin/end: every isect [0] and drain [1] launch
     // interval (scene clock) of the renders collected in between, so the union
     // across overlapping queued renders is exact (not one render's span less
@@ -231,6 +235,8 @@ struct spt::Workspace {
     void release() {
         for (WorkSet& w : sets) w.release();
         if (epoch) (void)hipEventDestroy(epoch);
+        hfree(list_bad);
+        if (list_bad_host) (void)hipHostFree(list_bad_host);
         for (JumpTable& t : jt) t.release();
         for (RenderSlot& r : slots) {
             hfree(r.dev);
@@ -506,6 +512,7 @@ spt_status render_slot(Workspace& ws, RenderSlot** out) {
     r.timed.clear();
     r.rs = spt_render_stats{};
     r.timing = false;
+    r.empty = false;
     *out = &r;
     return SPT_OK;
 }
@@ -533,7 +540,7 @@ spt_status render_collect(RenderSlot& r, Workspace& ws, spt_render_stats* out) {
     const hipEvent_t epoch = ws.epoch;
     spt_render_stats rs = r.rs;
     r.pending = false;
-    if (rs.tile_rows) {  // an empty tile queued nothing
+    if (rs.tile_rows && !r.empty) {  // an empty tile (or pixel list) queued nothing
         HIP_TRY(hipEventSynchronize(r.done));
         const unsigned long long* hstats = reinterpret_cast<const unsigned long long*>(r.host);
         static_assert(sizeof(Stats) == 13 * sizeof(unsigned long long), "Stats is the 13 counters read back here");
@@ -631,10 +638,24 @@ bool ranges_overlap(const void* a, const void* b, uint64_t n) {
     return x < y ? y - x < n : x - y < n;
 }
 
-// The argument checks of spt_render_async (accum_call false) and
-// spt_render_accum_async; *rows_out: the tile's rows.
+// Byte ranges [a, a + na) and [b, b + nb) overlap (either may be null or empty: no range).
+bool ranges_overlap2(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y ? y - x < na : x - y < nb;
+}
+
+// The argument checks of spt_render_async (accum_call false),
+// spt_render_accum_async and spt_render_accum_list (list_call); *rows_out: the
+// tile's rows.
 spt_status check_render_args(spt_scene sc, const spt_render_params* pp, const float* film_dev, const spt_accum* accum,
-                             bool accum_call, const uint64_t* ticket_out, uint32_t* rows_out) {
+                             bool accum_call, const uint64_t* ticket_out, uint32_t* rows_out,
+                             const spt_pixel_list* list = nullptr, bool list_call = false) {
+    if (list_call) {
+        if (!list) return fail(SPT_ERR_INVALID, "spt_render_accum_list: NULL list");
+        if (list->reserved != 0) return fail(SPT_ERR_INVALID, "spt_render_accum_list: reserved must be 0");
+        if (list->n && !list->pixels) return fail(SPT_ERR_INVALID, "spt_render_accum_list: NULL pixels");
+    }
     if (!sc || !pp || !ticket_out) return fail(SPT_ERR_INVALID, "spt_render: NULL argument");
     if (accum_call) {
         if (!accum || !accum->sum) return fail(SPT_ERR_INVALID, "spt_render_accum: NULL accumulator / sum");
@@ -664,6 +685,21 @@ spt_status check_render_args(spt_scene sc, const spt_render_params* pp, const fl
             for (int j = i + 1; j < 4; j++)
                 if (planes[i] && (planes[i] == planes[j] || ranges_overlap(planes[i], planes[j], 12ull * P)))
                     return fail(SPT_ERR_INVALID, "spt_render_accum: sum, sum_sq, film and variance must not overlap");
+        if (list_call) {
+            if (list->n > P)
+                return fail(SPT_ERR_INVALID, "spt_render_accum_list: %u listed pixels, the tile has %llu", list->n,
+                            (unsigned long long)P);
+            if (((uintptr_t)list->pixels | (uintptr_t)list->count) & 3u)
+                return fail(SPT_ERR_INVALID, "spt_render_accum_list: pixels and count must be 4-byte aligned");
+            const uint64_t nl = 4ull * list->n, nc = 4ull * P;
+            bool bad = ranges_overlap2(list->pixels, nl, list->count, nc);
+            for (int i = 0; i < 4; i++)
+                bad = bad || ranges_overlap2(planes[i], 12ull * P, list->pixels, nl) ||
+                      ranges_overlap2(planes[i], 12ull * P, list->count, nc);
+            if (bad)
+                return fail(SPT_ERR_INVALID, "spt_render_accum_list: pixels and count must not overlap each other or "
+                            "sum, sum_sq, film, variance");
+        }
     }
     *rows_out = rows;
     return SPT_OK;
@@ -681,8 +717,10 @@ bool device_free_bytes(void*, uint64_t* out) {
 }
 
 // What plan_render reads of this render (render_plan.h).
-RenderPlanIn plan_inputs(const spt_scene_t* sc, const spt_render_params& p, uint64_t P, hipStream_t caller) {
+RenderPlanIn plan_inputs(const spt_scene_t* sc, const spt_render_params& p, uint64_t P, uint64_t A,
+                         hipStream_t caller) {
     RenderPlanIn in;
+    in.A = A;
     in.P = P; in.spp = p.spp; in.flags = p.flags; in.wavefront_paths = p.wavefront_paths;
     in.cfg = &sc->cfg;
     // What a path carries (spt_internal.h PathMode): the reference's case
@@ -760,6 +798,10 @@ struct RenderJob {
     float* film_dev;
     const spt_accum* accum;
     uint64_t P;
+    // the pixels that take samples: P, or the n of spt_render_accum_list's list
+    // (work items count A per sample; film slots stay P per sample)
+    uint64_t A;
+    const spt_pixel_list* list;
     uint32_t s_begin, s_end;  // the samples [sample_base, sample_base + spp)
     const PcgJump *jumps, *cjumps;
     Camera cam;
@@ -806,6 +848,11 @@ struct RenderJob {
             ra.order = film_order;
             ra.env_r = p.env[0]; ra.env_g = p.env[1]; ra.env_b = p.env[2];
             ra.unwritten = &slot.dev->unwritten;
+            if (list) {
+                const ResolveListArgs la{ra, list->pixels, list->n, list->count};
+                return pl.mode == kModeUnit ? launch_resolve_flags_accum_list(sflag(), la, stream)
+                                            : launch_resolve_accum_list(sfilm(), la, stream);
+            }
             return pl.mode == kModeUnit ? launch_resolve_flags_accum(sflag(), ra, stream)
                                         : launch_resolve_accum(sfilm(), ra, stream);
         }
@@ -859,6 +906,10 @@ FusedArgs lane_loop_args(const RenderJob& j, const Sub& b, bool drain) {
     FusedArgs F{};
     fill_shade_args(F, j);
     F.cam = j.cam;
+    if (j.list && !drain) {
+        F.list = j.list->pixels;
+        F.list_n = j.list->n;
+    }
     F.stats = j.slot.dev->stats;
     F.next = &b.cnt->isect_next;  // (drain: zeroed by the refill before; an isect that skips leaves it)
     F.xcd_next = j.pl.lane_xcd ? &b.cnt->xcd_next[0][0] : nullptr;  // (drain: zeroed by the refill before)
@@ -912,6 +963,10 @@ void init_sub_run(SubRun& r, const RenderJob& j, const Sub& b) {
     RefillArgs& R = r.ra;
     fill_tile_args(R, j);
     R.cam = j.cam;
+    if (j.list) {
+        R.list = j.list->pixels;
+        R.list_n = j.list->n;
+    }
     R.stats = j.slot.dev->stats;
     R.capacity = (uint32_t)b.cap;
     R.pixel_block = cfg.pixel_block;
@@ -936,8 +991,8 @@ spt_status enqueue_fused(RenderJob& j, uint64_t* iters, uint32_t* lanes) {
     spt_status st;
     for (uint32_t s0 = j.s_begin; s0 < j.s_end; s0 += j.pl.chunk) {
         const uint32_t ns = std::min(j.pl.chunk, j.s_end - s0);
-        F.work0 = (uint64_t)s0 * j.P;
-        F.count = (uint32_t)((uint64_t)ns * j.P);  // <= 4 GiB / 12 B per chunk
+        F.work0 = (uint64_t)s0 * j.A;
+        F.count = (uint32_t)((uint64_t)ns * j.A);  // <= 4 GiB / 12 B per chunk
         F.sample0 = s0;
         F.pm_ns = j.pl.pixel_major ? ns : 0;
         HIP_TRY(j.clear_film(ns));
@@ -957,7 +1012,7 @@ spt_status first_refill(RenderJob& j, SubRun& r, int k, uint32_t s0, uint32_t ns
     Sub& b = j.ws.sub[k];
     const hipStream_t sk = b.stream;
     const int K = pl.K;
-    const uint64_t w0 = (uint64_t)s0 * j.P, L = (uint64_t)ns * j.P;
+    const uint64_t w0 = (uint64_t)s0 * j.A, L = (uint64_t)ns * j.A;
     // contiguous share of the chunk's work items (sample-major); pixel-major
     // work splits the chunk's samples instead, so that every stream
     // covers the whole tile (a band of rows per stream would leave the
@@ -966,7 +1021,7 @@ spt_status first_refill(RenderJob& j, SubRun& r, int k, uint32_t s0, uint32_t ns
     r.ra.chunk_s0 = s0; r.ra.chunk_ns = ns;
     if (r.ra.work_order && ns >= (uint32_t)K) {
         const uint32_t sk0 = s0 + ns * k / K, sk1 = s0 + ns * (k + 1) / K;
-        wb = (uint64_t)sk0 * j.P; we = (uint64_t)sk1 * j.P;
+        wb = (uint64_t)sk0 * j.A; we = (uint64_t)sk1 * j.A;
         r.ra.chunk_s0 = sk0; r.ra.chunk_ns = sk1 - sk0;
     }
     HIP_TRY(hipMemsetAsync(b.cnt, 0, sizeof(Counters), sk));
@@ -1190,7 +1245,7 @@ spt_status enqueue_wavefront_chunk(RenderJob& j, SubRun* runs, uint32_t s0, uint
     // later: the loop stops there without a further readback.  Live counts
     // never grow after that, so a stale count is a safe grid size, and a
     // refill's grid is bounded by the work not yet known to be started.
-    const uint64_t L = (uint64_t)ns * j.P;
+    const uint64_t L = (uint64_t)ns * j.A;
     const uint64_t max_iters = (L * j.p.max_depth + j.pl.Ck - 1) / j.pl.Ck + j.p.max_depth + 64;
     uint64_t it = 0;
     const uint32_t batch = 4;
@@ -1226,11 +1281,11 @@ spt_status enqueue_wavefront_chunk(RenderJob& j, SubRun* runs, uint32_t s0, uint
 // The plan of this render and a working set that holds it: plan_render, then
 // ensure_workspace; a set that could not be allocated frees its queues and
 // the plan is made again with half the paths in flight as the limit.
-spt_status plan_and_allocate(spt_scene_t* sc, const spt_render_params& p, uint64_t P, hipStream_t caller,
+spt_status plan_and_allocate(spt_scene_t* sc, const spt_render_params& p, uint64_t P, uint64_t A, hipStream_t caller,
                              spt_render_stats& rs, RenderPlan* plan, WorkSet** set) {
     const spt_config& cfg = sc->cfg;
     for (uint64_t fit_limit = UINT64_MAX;;) {
-        const RenderPlanIn in = plan_inputs(sc, p, P, caller);
+        const RenderPlanIn in = plan_inputs(sc, p, P, A, caller);
         const RenderPlan pl = plan_render(in, fit_limit);
         rs.fit_paths = pl.fit_paths;
         if (pl.limit)
@@ -1262,11 +1317,14 @@ spt_status plan_and_allocate(spt_scene_t* sc, const spt_render_params& p, uint64
 // working set) and spt_render_accum_async (accum: samples [sample_base,
 // sample_base + spp) added onto the caller's sums) — one render loop; the two
 // differ in where the jump table is read and in the resolve.
+// With `list` (spt_render_accum_list): the pass over the listed pixels; the
+// list is checked on the device first, and the caller's stream waited for.
 spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film_dev, const spt_accum* accum,
-                          bool accum_call, void* caller_, uint64_t* ticket_out) {
+                          bool accum_call, void* caller_, uint64_t* ticket_out, const spt_pixel_list* list = nullptr,
+                          bool list_call = false) {
     const double wall0 = now_ms();
     uint32_t rows = 0;
-    spt_status st = check_render_args(sc, pp, film_dev, accum, accum_call, ticket_out, &rows);
+    spt_status st = check_render_args(sc, pp, film_dev, accum, accum_call, ticket_out, &rows, list, list_call);
     if (st) return st;
     const spt_render_params& p = *pp;
     // The caller's stream orders the render with the caller's work (it starts
@@ -1282,15 +1340,30 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
     spt_render_stats& rs = slot->rs;
     rs.tile_rows = rows;
     slot->wall0 = wall0;
-    if (P == 0) {  // an empty tile: nothing to render, film untouched
+    if (P == 0 || (list_call && list->n == 0)) {  // an empty tile or list: nothing to render, film untouched
+        slot->empty = true;
         slot->ticket = sc->ws.next_ticket++;
         slot->pending = true;
         *ticket_out = slot->ticket;
         return SPT_OK;
     }
+    if (list_call) {
+        // strictly ascending and in range, or nothing is written
+        Workspace& w = sc->ws;
+        if (!w.list_bad) HIP_TRY(hipMalloc((void**)&w.list_bad, sizeof(uint32_t)));
+        if (!w.list_bad_host) HIP_TRY(hipHostMalloc((void**)&w.list_bad_host, sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(hipMemsetAsync(w.list_bad, 0, sizeof(uint32_t), caller));
+        HIP_TRY(launch_list_validate(list->pixels, list->n, (uint32_t)P, w.list_bad, caller));
+        HIP_TRY(hipMemcpyAsync(w.list_bad_host, w.list_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, caller));
+        HIP_TRY(hipStreamSynchronize(caller));
+        if (*w.list_bad_host)
+            return fail(SPT_ERR_INVALID, "spt_render_accum_list: pixels must be strictly ascending and < %llu",
+                        (unsigned long long)P);
+    }
+    const uint64_t A = list_call ? list->n : 0;  // 0: every tile pixel
     RenderPlan pl;
     WorkSet* set = nullptr;
-    if ((st = plan_and_allocate(sc, p, P, caller, rs, &pl, &set))) return st;
+    if ((st = plan_and_allocate(sc, p, P, A, caller, rs, &pl, &set))) return st;
     WorkSet& ws = *set;
     const int K = pl.K;
     // the set's stream 0 (its own): the render's first and last launches, the
@@ -1306,7 +1379,8 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
     // (rr_uniform), so sample s of a pass is sample s of any render
     const int set_idx = (int)(&ws - sc->ws.sets);
     const bool timing = (p.flags & SPT_FLAG_TIMING) != 0;
-    RenderJob job{sc, p, pl, ws, *slot, film_dev, accum, P, sample_base, sample_base + p.spp, jtab->samples(),
+    RenderJob job{sc, p, pl, ws, *slot, film_dev, accum, P, A ? A : P, list_call ? list : nullptr, sample_base,
+                  sample_base + p.spp, jtab->samples(),
                   jtab->casts(), make_camera(p), stream, timing, timing && (p.flags & SPT_FLAG_TIMING_ALL) != 0};
     // the set's previous render (another stream, perhaps) must be done with it
     if (ws.used) HIP_TRY(hipStreamWaitEvent(stream, ws.free_ev, 0));
@@ -1354,7 +1428,7 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
     rs.streams = (uint32_t)K;
     rs.fused = pl.fused ? 1u : 0u;
     rs.drain_refill_idle = !pl.fused && pl.drain_on ? pl.drain_idle : 0u;
-    slot->regen_base = std::min<uint64_t>(C, P * p.spp);
+    slot->regen_base = std::min<uint64_t>(C, job.A * p.spp);
     slot->ticket = sc->ws.next_ticket++;
     slot->pending = true;
     *ticket_out = slot->ticket;
@@ -1381,6 +1455,14 @@ spt_status spt_render_accum(spt_scene sc, const spt_render_params* pp, const spt
                             spt_render_stats* stats_out, void* stream) {
     uint64_t ticket = 0;
     spt_status st = spt_render_accum_async(sc, pp, acc, stream, &ticket);
+    if (st) return st;
+    return spt_render_wait(sc, ticket, stats_out);
+}
+
+spt_status spt_render_accum_list(spt_scene sc, const spt_render_params* pp, const spt_accum* acc,
+                                 const spt_pixel_list* list, spt_render_stats* stats_out, void* stream) {
+    uint64_t ticket = 0;
+    spt_status st = render_enqueue(sc, pp, nullptr, acc, true, stream, &ticket, list, true);
     if (st) return st;
     return spt_render_wait(sc, ticket, stats_out);
 }

@@ -59,6 +59,12 @@ struct RenderPlanIn {
     // the params: the tile's pixels, samples, SPT_FLAG_*, the explicit paths in flight (0: the config's)
     uint64_t P = 0;
     uint32_t spp = 0, flags = 0, wavefront_paths = 0;
+    // spt_render_accum_list: the listed pixels, the only ones that take samples
+    // (0: no list, every tile pixel).  The job is A x spp work items — the
+    // pipeline, the fit and the paths in flight follow it — while the film
+    // chunk keeps a slot per tile pixel and sample (P), since a path's slot is
+    // indexed by its tile pixel
+    uint64_t A = 0;
     const spt_config* cfg = nullptr;
     // the scene: its path mode (spt_internal.h PathMode) with the mode's 16-B
     // queue planes and film bytes per path, the bytes of its device arrays, its
@@ -112,7 +118,7 @@ struct RenderPlan {
 // half the paths that attempt had in flight.
 inline RenderPlan plan_render(const RenderPlanIn& in, uint64_t fit_limit) {
     const spt_config& cfg = *in.cfg;
-    const uint64_t P = in.P, jobs = in.P * in.spp;
+    const uint64_t P = in.P, A = in.A ? in.A : in.P, jobs = A * in.spp;
     RenderPlan pl;
     pl.mode = in.mode;
     bool& fused = pl.fused;
@@ -196,8 +202,8 @@ inline RenderPlan plan_render(const RenderPlanIn& in, uint64_t fit_limit) {
     }
     const bool fit_ok = !fused && !in.wavefront_paths && cfg.wavefront_paths == kDefaultWavefrontPaths && fit_paths &&
                         cfg.drain_q8;
-    if (fit_ok && jobs > fit_paths && cfg.fit_chunks && P <= fit_paths)
-        fit_chunk = (uint32_t)std::min<uint64_t>(in.spp, fit_paths / P);
+    if (fit_ok && jobs > fit_paths && cfg.fit_chunks && A <= fit_paths)
+        fit_chunk = (uint32_t)std::min<uint64_t>(in.spp, fit_paths / A);
     const bool fit = pl.fit = fit_ok && (jobs <= fit_paths || fit_chunk != 0);
     const uint64_t scene_bytes = in.device_bytes;
     // (a fitting job of any tile size: pixel-major over scenes beyond an
@@ -231,7 +237,7 @@ inline RenderPlan plan_render(const RenderPlanIn& in, uint64_t fit_limit) {
                     : pl.queue_nt ? kDrainIdleStream : kDrainIdleCached;
     if (cfg.work_order == SPT_WORK_AUTO && wave_pm && !in.wavefront_paths && cfg.wavefront_paths == kDefaultWavefrontPaths)
         C = kPixelMajorWavefrontPaths;
-    if (fit) C = fit_chunk ? (uint64_t)fit_chunk * P : jobs;
+    if (fit) C = fit_chunk ? (uint64_t)fit_chunk * A : jobs;
     C = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(C, mem_paths), jobs));
     if (C >= (1ull << 31)) {
         pl.limit = true;

@@ -93,6 +93,11 @@ class Scene {
                       void* stream = nullptr) {
         check(spt_render_accum(scene_, &p, &acc, stats, stream), "spt_render_accum");
     }
+    // spt_render_accum_list: the same pass over the listed tile pixels only
+    void render_accum_list(const spt_render_params& p, const spt_accum& acc, const spt_pixel_list& list,
+                           spt_render_stats* stats, void* stream = nullptr) {
+        check(spt_render_accum_list(scene_, &p, &acc, &list, stats, stream), "spt_render_accum_list");
+    }
     // spt_render_aov: the first-hit buffers of p's tile, queued on `stream`
     void render_aov(const spt_render_params& p, const spt_aov& planes, void* stream = nullptr) {
         check(spt_render_aov(scene_, &p, &planes, stream), "spt_render_aov");
@@ -196,6 +201,16 @@ inline void denoise_var(const spt_denoise_var_params& p, const float* color, con
     check(spt_denoise_var(&p, color, variance, guides, out, variance_out, scratch.get(), stream), "spt_denoise_var");
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
         throw std::runtime_error("spt::denoise_var: stream failed");
+}
+
+// spt_adapt_select with scratch the caller sized (spt_adapt_select_scratch_bytes):
+// the active pixels of an accumulation, ascending, in list; returns their number.
+inline uint32_t adapt_select(const spt_adapt_params& p, uint32_t npix, uint32_t sample_base, const float* sum,
+                             const float* sum_sq, const uint32_t* count, uint32_t* list, void* scratch,
+                             void* stream = nullptr) {
+    uint32_t n = 0;
+    check(spt_adapt_select(&p, npix, sample_base, sum, sum_sq, count, list, &n, scratch, stream), "spt_adapt_select");
+    return n;
 }
 
 }  // namespace spt

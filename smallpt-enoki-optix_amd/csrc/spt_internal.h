@@ -246,6 +246,11 @@ struct RefillArgs {
                                 // makes, traces and shades the paths this refill starts)
     const uint32_t* surv_shards;  // non-null: the survivors are the sum of these kShards counters
                                   // (kShardStride apart; a sharded shade: ShadeArgs::shard_items)
+    // spt_render_accum_list (the kList kernels only): work items run over the
+    // list_n listed pixels instead of the tile's P, pixel index q -> tile pixel
+    // list[q] (scanline; no pixel blocks); the path keeps the tile pixel
+    const uint32_t* list;
+    uint32_t list_n;
 };
 
 struct IsectQueueArgs {
@@ -398,6 +403,9 @@ struct FusedArgs {
     uint32_t seg_items, seg_block;
     uint32_t count_queue;           // 1: add the queue's paths (their casts here) to stats[0] (a forced
                                     // drain, which no bookkeeping refill follows)
+    // spt_render_accum_list (the kList fused kernels only): as RefillArgs::list
+    const uint32_t* list;
+    uint32_t list_n;
 };
 
 struct HitInfoArgs {
@@ -531,6 +539,36 @@ struct ResolveAccumArgs {
 };
 hipError_t launch_resolve_accum(const float* sfilm, const ResolveAccumArgs& a, hipStream_t s);
 hipError_t launch_resolve_flags_accum(const uint8_t* sflag, const ResolveAccumArgs& a, hipStream_t s);
+// spt_render_accum_list's resolves: lane j does for tile pixel pixels[j] what
+// the two above do for pixel j, and on the last chunk sets count[pixels[j]] =
+// n_total (count may be null); nothing else is written.
+struct ResolveListArgs {
+    ResolveAccumArgs r;         // P: the tile's pixels (the planes' and the film chunk's stride)
+    const uint32_t* pixels;
+    uint32_t n;
+    uint32_t* count;
+};
+hipError_t launch_resolve_accum_list(const float* sfilm, const ResolveListArgs& a, hipStream_t s);
+hipError_t launch_resolve_flags_accum_list(const uint8_t* sflag, const ResolveListArgs& a, hipStream_t s);
+// *bad = 1 unless pixels[0 .. n) is strictly ascending with every entry < P (*bad zeroed before)
+hipError_t launch_list_validate(const uint32_t* pixels, uint32_t n, uint32_t P, uint32_t* bad, hipStream_t s);
+
+// ---- adaptive selection (adapt.hip, spt_adapt_select)
+struct AdaptArgs {
+    const float* sum;
+    const float* sum_sq;
+    const uint32_t* count;
+    uint32_t* list;
+    uint32_t* masks;            // scratch: two words (lo, hi) per 64 pixels, the wave's ballot
+    uint32_t* totals;           // scratch: blocks + 1 words; block totals, then their exclusive scan and the sum
+    uint32_t npix, n;           // n: sample_base
+    uint32_t min_spp, max_spp;
+    float tolerance, floor;
+};
+constexpr uint32_t kAdaptBlock = 256;
+// count + scan + write (n > 0), or the identity list (n == 0: no input is
+// read); the active count ends in totals[blocks] (n > 0 only)
+hipError_t launch_adapt_select(const AdaptArgs& a, hipStream_t s);
 hipError_t launch_hit_info(const HitInfoArgs& a, hipStream_t s);
 
 // ---- in-place geometry update (refit.hip, spt_scene_update_geometry)

@@ -41,6 +41,7 @@ EXPORTED = [
     "spt_scene_update_geometry", "spt_scene_update_geometry_device", "spt_scene_get_refit_stats",
     "spt_render_accum", "spt_render_accum_async",
     "spt_default_denoise_var_params", "spt_denoise_var_scratch_bytes", "spt_denoise_var",
+    "spt_default_adapt_params", "spt_adapt_select_scratch_bytes", "spt_adapt_select", "spt_render_accum_list",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -189,6 +190,17 @@ class Accum(ctypes.Structure):
                 ("film", c_void_p), ("variance", c_void_p)]
 
 
+class AdaptParams(ctypes.Structure):
+    """spt_adapt_params: which pixels spt_adapt_select keeps sampling."""
+    _fields_ = [("min_spp", c_uint32), ("max_spp", c_uint32), ("tolerance", c_float), ("floor", c_float),
+                ("reserved", c_uint32 * 2)]
+
+
+class PixelList(ctypes.Structure):
+    """spt_pixel_list: the tile pixels of one spt_render_accum_list pass."""
+    _fields_ = [("pixels", c_void_p), ("n", c_uint32), ("reserved", c_uint32), ("count", c_void_p)]
+
+
 def _load() -> ctypes.CDLL:
     # torch ships its own HIP runtime (SONAME libamdhip64.so.7).  Load it first
     # so libspt.so binds to that one copy: loading libspt.so first would map the
@@ -249,6 +261,11 @@ def _load() -> ctypes.CDLL:
         "spt_default_denoise_var_params": (None, [POINTER(DenoiseVarParams)]),
         "spt_denoise_var_scratch_bytes": (ctypes.c_size_t, [u32, u32]),
         "spt_denoise_var": (i32, [POINTER(DenoiseVarParams), vp, vp, POINTER(Aov), vp, vp, vp, vp]),
+        "spt_default_adapt_params": (None, [POINTER(AdaptParams)]),
+        "spt_adapt_select_scratch_bytes": (ctypes.c_size_t, [u32]),
+        "spt_adapt_select": (i32, [POINTER(AdaptParams), u32, u32, vp, vp, vp, vp, POINTER(u32), vp, vp]),
+        "spt_render_accum_list": (i32, [vp, POINTER(RenderParams), POINTER(Accum), POINTER(PixelList),
+                                        POINTER(RenderStats), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -280,6 +297,12 @@ def default_denoise_params() -> DenoiseParams:
 def default_denoise_var_params() -> DenoiseVarParams:
     p = DenoiseVarParams()
     lib.spt_default_denoise_var_params(ctypes.byref(p))
+    return p
+
+
+def default_adapt_params() -> AdaptParams:
+    p = AdaptParams()
+    lib.spt_default_adapt_params(ctypes.byref(p))
     return p
 
 
@@ -383,7 +406,8 @@ def tile_rows(height: int, tile_index: int, tile_count: int, rows_per_group: int
 __all__ = [
     "lib", "check", "SptError", "Rays", "Hits", "HitInfo", "Camera", "RenderParams", "RenderStats",
     "SceneStats", "RefitStats", "Mesh", "Config", "Aov", "AOV_PLANES", "DenoiseParams", "default_denoise_params",
-    "DenoiseVarParams", "default_denoise_var_params", "Accum", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
+    "DenoiseVarParams", "default_denoise_var_params", "Accum",
+    "AdaptParams", "PixelList", "default_adapt_params", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
     "LIB_PATH", "REPO_ROOT",
     "PCG32_DEFAULT_STATE", "SPT_RNG_Y_FIRST", "SPT_RNG_X_FIRST", "SPT_FLAG_TIMING", "c_uint8",
 ]

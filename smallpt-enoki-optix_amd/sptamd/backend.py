@@ -609,7 +609,14 @@ class Accumulator:
     stream need no synchronisation in between).  film, variance, sum and sum_sq
     are (3, rows, W) float32 device tensors, current once the last pass has run
     on its stream; any split of N samples into passes gives the same bits, and
-    film is Scene.render's at spp = N (include/spt.h)."""
+    film is Scene.render's at spp = N (include/spt.h).
+
+    Adaptive sampling: add_list(spp, pixels) renders the next spp samples of
+    the listed tile pixels only (spt_render_accum_list), add_adaptive(spp, ...)
+    of the pixels spt_adapt_select finds unconverged.  count (rows, W; int32
+    holding the uint32 values) is the number of samples each pixel's sums hold,
+    samples the largest of them.  After a sparse pass add() raises: the pixels'
+    sums are no longer prefixes of one length."""
 
     def __init__(self, scene: "Scene", params: RenderParams, moments: bool = True):
         self.scene = scene
@@ -620,13 +627,30 @@ class Accumulator:
         self.film = torch.zeros(shape, dtype=torch.float32, device=dev)
         self.sum_sq = torch.zeros(shape, dtype=torch.float32, device=dev) if moments else None
         self.variance = torch.zeros(shape, dtype=torch.float32, device=dev) if moments else None
+        self._count = torch.zeros(shape[1:], dtype=torch.int32, device=dev)
+        self._count_stale = False       # every pixel holds `samples` (add keeps no per-pixel books)
         self.samples = 0
+        self.sparse = False
+        self._list = self._scratch = None
+
+    @property
+    def count(self) -> torch.Tensor:
+        """(rows, W) int32: the samples each pixel's sums hold."""
+        if self._count_stale:
+            self._count.fill_(self.samples)
+            self._count_stale = False
+        return self._count
 
     def reset(self) -> None:
         """Start over: the next add renders sample 0 (the planes are rewritten by it)."""
         self.samples = 0
+        self.sparse = False
+        self._count_stale = True
 
-    def _acc(self, spp: int) -> _lib.Accum:
+    def _acc(self, spp: int, sparse: bool = False) -> _lib.Accum:
+        if self.sparse and not sparse:
+            raise RuntimeError("Accumulator.add after a sparse pass: the pixels hold different sample counts "
+                               "(use add_list / add_adaptive, or reset)")
         if spp <= 0:
             raise ValueError("Accumulator.add: spp must be > 0")
         self.params.spp = spp
@@ -644,7 +668,56 @@ class Accumulator:
         check(lib.spt_render_accum(self.scene.backend.handle, ctypes.byref(self.params), ctypes.byref(a),
                                    ctypes.byref(st), _stream_handle(stream)), "spt_render_accum")
         self.samples += spp
+        self._count_stale = True
         return st.as_dict()
+
+    def add_list(self, spp: int, pixels: torch.Tensor, n: Optional[int] = None, stream=None) -> dict:
+        """spt_render_accum_list: samples [samples, samples + spp) of the tile
+        pixels pixels[:n] (an int32 device tensor of strictly ascending tile
+        pixel indices) onto their sums; count becomes samples + spp there.
+        Synchronous; returns the pass's stats."""
+        assert pixels.is_cuda and pixels.is_contiguous() and pixels.dtype == torch.int32, \
+            "pixels must be a contiguous int32 device tensor"
+        n = pixels.numel() if n is None else int(n)
+        assert 0 <= n <= pixels.numel()
+        a, st = self._acc(spp, sparse=True), RenderStats()
+        if stream is not None:
+            with torch.cuda.stream(stream):  # the fill, if one is due, goes where the pass runs
+                self.count
+        pl = _lib.PixelList()
+        pl.pixels, pl.n, pl.count = pixels.data_ptr(), n, self.count.data_ptr()
+        self.scene.backend.sync_config()
+        check(lib.spt_render_accum_list(self.scene.backend.handle, ctypes.byref(self.params), ctypes.byref(a),
+                                        ctypes.byref(pl), ctypes.byref(st), _stream_handle(stream)),
+              "spt_render_accum_list")
+        if n:
+            self.samples += spp
+        if n != self.count.numel():
+            self.sparse = True
+        return st.as_dict()
+
+    def add_adaptive(self, spp: int, tolerance: Optional[float] = None, min_spp: Optional[int] = None,
+                     max_spp: Optional[int] = None, floor: Optional[float] = None, stream=None) -> dict:
+        """One adaptive pass: spt_adapt_select over the sums (the pixels that
+        hold `samples` samples and are short of min_spp, or below max_spp and
+        not converged to `tolerance`), then add_list(spp) over them.  Returns
+        the pass's stats plus "active", the number of pixels sampled (0: done).
+        Parameters default to spt_default_adapt_params.  Needs the moments."""
+        if self.sum_sq is None:
+            raise RuntimeError("Accumulator.add_adaptive needs moments=True")
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                self.count
+        npix = self.count.numel()
+        if self._list is None:
+            dev = self.count.device
+            self._list = torch.empty(max(1, npix), dtype=torch.int32, device=dev)
+            self._scratch = torch.empty(lib.spt_adapt_select_scratch_bytes(npix), dtype=torch.uint8, device=dev)
+        n = adapt_select(self.sum, self.sum_sq, self.count, self.samples, tolerance=tolerance, min_spp=min_spp,
+                         max_spp=max_spp, floor=floor, out=self._list, scratch=self._scratch, stream=stream)
+        st = self.add_list(spp, self._list, n, stream=stream)
+        st["active"] = n
+        return st
 
     def add_async(self, spp: int, stream=None) -> int:
         """Queue the pass and return its ticket (collect it with wait)."""
@@ -653,11 +726,43 @@ class Accumulator:
         check(lib.spt_render_accum_async(self.scene.backend.handle, ctypes.byref(self.params), ctypes.byref(a),
                                          _stream_handle(stream), ctypes.byref(ticket)), "spt_render_accum_async")
         self.samples += spp
+        self._count_stale = True
         return ticket.value
 
     def wait(self, ticket: int) -> dict:
         """The stats of a queued pass (waits for it)."""
         return self.scene.render_wait(ticket)
+
+
+def adapt_select(sum: torch.Tensor, sum_sq: torch.Tensor, count: torch.Tensor, sample_base: int,
+                 tolerance: Optional[float] = None, min_spp: Optional[int] = None, max_spp: Optional[int] = None,
+                 floor: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                 scratch: Optional[torch.Tensor] = None, stream=None):
+    """spt_adapt_select: the pixels of an accumulation (sum, sum_sq: (3, ...)
+    float32 planes, count: int32 samples per pixel) that a pass starting at
+    sample_base must still sample, ascending.  Returns the list (an int32
+    device tensor of that length), or with `out` (int32, one entry per pixel;
+    only the head is written) just their number.  Parameters default to
+    spt_default_adapt_params.  Waits for `stream` (default: the current one)."""
+    npix = count.numel()
+    for t, name, k in ((sum, "sum", 3), (sum_sq, "sum_sq", 3), (count, "count", 1)):
+        assert t.is_cuda and t.is_contiguous() and t.numel() == k * npix, f"{name}: a contiguous device tensor"
+    assert sum.dtype == torch.float32 and sum_sq.dtype == torch.float32 and count.dtype == torch.int32
+    p = _lib.default_adapt_params()
+    for k, v in (("tolerance", tolerance), ("min_spp", min_spp), ("max_spp", max_spp), ("floor", floor)):
+        if v is not None:
+            setattr(p, k, v)
+    s = stream if stream is not None else torch.cuda.current_stream(count.device)
+    with torch.cuda.stream(s):
+        lst = torch.empty(max(1, npix), dtype=torch.int32, device=count.device) if out is None else out
+        if scratch is None:
+            scratch = torch.empty(lib.spt_adapt_select_scratch_bytes(npix), dtype=torch.uint8, device=count.device)
+    assert lst.is_contiguous() and lst.dtype == torch.int32 and lst.numel() >= npix
+    n = ctypes.c_uint32()
+    check(lib.spt_adapt_select(ctypes.byref(p), npix, sample_base, sum.data_ptr(), sum_sq.data_ptr(), count.data_ptr(),
+                               lst.data_ptr(), ctypes.byref(n), scratch.data_ptr(), s.cuda_stream or None),
+          "spt_adapt_select")
+    return n.value if out is not None else lst[: n.value]
 
 
 def aov_struct(aov: Optional[dict]) -> _lib.Aov:
