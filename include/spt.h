@@ -401,6 +401,33 @@ enum { SPT_MAT_DIFFUSE = 0, SPT_MAT_MIRROR = 1, SPT_MAT_GLASS = 2 };
 spt_status spt_scene_set_spheres(spt_scene scene, const float* center_radius, const int32_t* mat_id, uint32_t n);
 spt_status spt_scene_set_material_kinds(spt_scene scene, const uint32_t* kinds, uint32_t nmat);
 
+/* Environment-map lighting (a build addition, the reference's
+ * sky is the constant 1, main.cpp:407).  A scene may hold one octahedral sky
+ * image: n x n interleaved RGB floats (1 <= n <= 4096), row j = b, column
+ * i = a, where for a direction e = rotation * d and s = |e.x| + |e.y| + |e.z|
+ * (a, b) = (e.x, e.y) / s on the upper hemisphere (e.z >= 0) and
+ * ((1 - |b|) sgn a, (1 - |a|) sgn b) of those on the lower one; texel centre
+ * (i + 1/2, j + 1/2) / n = (a, b) / 2 + 1/2.  The +z pole is the image centre,
+ * the four corners are the -z pole.  A path that escapes in direction d (any
+ * length) then adds throughput x params.env x M(d), M the bilinear lookup
+ * across the octahedral edges, instead of throughput x params.env.  Every
+ * operation is f32 and rounded once, in the order DESIGN.md §13 lists.
+ *
+ * rotation: 9 floats row-major world -> map, NULL = identity; rgb NULL removes
+ * the map (n and rotation are then ignored).  Like the other setters it waits
+ * for queued renders and public calls first.  SPT_ERR_INVALID: NULL scene,
+ * n = 0 with an image, a texel or rotation entry that is not finite;
+ * SPT_ERR_LIMIT: n > 4096; the scene is unchanged after an error.
+ * spt_render_aov and spt_intersect do not read the map.  spt_scene_save refuses
+ * a scene that holds one (the cache does not store it; set it after loading). */
+spt_status spt_scene_set_envmap(spt_scene scene, const float* rgb, uint32_t n, const float* rotation);
+
+/* Host only, no device: resample a lat-long image (w x h interleaved RGB, rows
+ * top-down; pbrt's convention theta = acos(z), phi = atan2(y, x), u = phi / 2pi
+ * wrapped, v = theta / pi clamped, bilinear) to the n x n octahedral texel
+ * centres; computed in f64, rounded once.  out_rgb: n x n x 3 floats. */
+spt_status spt_envmap_from_latlong(const float* rgb, uint32_t w, uint32_t h, uint32_t n, float* out_rgb);
+
 /* LambertBsdf's reflectance image for one material (ImageTexture,
  * main.cpp:34-80; the reference only ever builds 1 x 1 images, main.cpp:40-44,
  * and its loader is empty, :37-39): rgb = width x height interleaved RGB
@@ -919,6 +946,14 @@ spt_status spt_pbrt_load(const char* path, spt_mesh* out, spt_pbrt_info* info);
  * rows bottom-up, scale -1 (little endian). */
 spt_status spt_pfm_write(const char* path, const float* r, const float* g, const float* b,
                          uint32_t width, uint32_t height);
+
+/* Reads what spt_pfm_write writes: a 3-channel "PF" file of either endianness
+ * (the sign of the scale), rows bottom-up in the file, returned top-down as
+ * width x height interleaved RGB floats (free with spt_pfm_free).
+ * SPT_ERR_IO: the file cannot be opened or is short; SPT_ERR_INVALID: not a
+ * 3-channel PFM, or a bad header. */
+spt_status spt_pfm_read(const char* path, float** rgb, uint32_t* width, uint32_t* height);
+void spt_pfm_free(float* rgb);
 
 #ifdef __cplusplus
 }

@@ -710,6 +710,62 @@ spt_status spt_scene_set_material_kinds(spt_scene sc, const uint32_t* kinds, uin
     return SPT_OK;
 }
 
+spt_status spt_scene_set_envmap(spt_scene sc, const float* rgb, uint32_t n, const float* rotation) {
+    static const char* what = "spt_scene_set_envmap";
+    if (!sc) return fail(SPT_ERR_INVALID, "%s: NULL scene", what);
+    // every refusal comes before the scene or the device is touched
+    if (rgb) {
+        if (n == 0) return fail(SPT_ERR_INVALID, "%s: n = 0 with an image", what);
+        if (n > kEnvMapMaxN) return fail(SPT_ERR_LIMIT, "%s: n = %u (at most %u)", what, n, kEnvMapMaxN);
+        for (int k = 0; rotation && k < 9; k++)
+            if (!std::isfinite(rotation[k])) return fail(SPT_ERR_INVALID, "%s: rotation entry %d is not finite", what, k);
+        for (size_t k = 0; k < (size_t)n * n * 3; k++)
+            if (!std::isfinite(rgb[k]))
+                return fail(SPT_ERR_INVALID, "%s: texel (%zu, %zu) channel %zu is not finite", what, (k / 3) % n,
+                            (k / 3) / n, k % 3);
+    }
+    DeviceGuard dg(sc->device);
+    DeviceEnvMap* d_map = nullptr;
+    float4* d_tex = nullptr;
+    if (rgb) {
+        // the image inside its gutter (DeviceEnvMap): gutter texels by the edge rule
+        const int32_t ni = (int32_t)n;
+        const size_t pitch = (size_t)n + 2;
+        std::vector<float4> tex(pitch * pitch);
+        for (int32_t j = -1; j <= ni; j++)
+            for (int32_t i = -1; i <= ni; i++) {
+                int32_t si = i, sj = j;
+                envmap_wrap(ni, si, sj);
+                const float* t = rgb + ((size_t)sj * n + (size_t)si) * 3;
+                tex[(size_t)(j + 1) * pitch + (size_t)(i + 1)] = make_float4(t[0], t[1], t[2], 0.0f);
+            }
+        DeviceEnvMap h;
+        h.n = n;
+        static const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        std::memcpy(h.rot, rotation ? rotation : ident, sizeof(h.rot));
+        spt_status us = upload(&d_tex, tex.data(), sizeof(float4) * tex.size());
+        h.texels = d_tex;
+        if (!us) us = upload(&d_map, &h, sizeof(h));
+        if (us) {
+            hfree(d_tex);
+            hfree(d_map);
+            return us;
+        }
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    spt_status qs = quiesce_scene(sc);  // queued renders may still read the old map
+    if (qs) {
+        hfree(d_tex);
+        hfree(d_map);
+        return qs;
+    }
+    hfree(sc->envmap);
+    hfree(sc->env_texels);
+    sc->envmap = d_map;
+    sc->env_texels = d_tex;
+    return SPT_OK;
+}
+
 namespace {
 
 // spt_scene_update_geometry[_device] once the arrays are on the device

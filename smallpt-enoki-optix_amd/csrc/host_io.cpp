@@ -7,6 +7,7 @@
 //                   with 0 the default material (main.cpp:185,229-245).
 //   spt_pfm_write : Fimage::save_pfm (fimage.h:33-58).
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -225,6 +226,97 @@ spt_status spt_pfm_write(const char* path, const float* r, const float* g, const
         }
     }
     return std::fclose(f) == 0 ? SPT_OK : spt_set_error(SPT_ERR_IO, "spt_pfm_write: closing %s failed", path);
+}
+
+spt_status spt_pfm_read(const char* path, float** rgb, uint32_t* w_out, uint32_t* h_out) {
+    if (!path || !rgb || !w_out || !h_out) return spt_set_error(SPT_ERR_INVALID, "spt_pfm_read: NULL argument");
+    *rgb = nullptr;
+    *w_out = *h_out = 0;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return spt_set_error(SPT_ERR_IO, "spt_pfm_read: cannot open %s: %s", path, std::strerror(errno));
+    char magic[3] = {0, 0, 0};
+    unsigned long w = 0, h = 0;
+    double scale = 0.0;
+    // "PF" w h scale, then exactly one whitespace byte before the data
+    if (std::fscanf(f, "%2s", magic) != 1 || std::strcmp(magic, "PF") != 0) {
+        std::fclose(f);
+        return spt_set_error(SPT_ERR_INVALID, "spt_pfm_read: %s is not a 3-channel PFM (magic '%s')", path, magic);
+    }
+    const bool head = std::fscanf(f, "%lu %lu %lf", &w, &h, &scale) == 3;
+    const int sep = head ? std::fgetc(f) : EOF;
+    if (!head || w == 0 || h == 0 || w > (1ul << 16) || h > (1ul << 16) || !(scale == scale) || scale == 0.0 ||
+        !(sep == '\n' || sep == ' ' || sep == '\r' || sep == '\t')) {
+        std::fclose(f);
+        return spt_set_error(SPT_ERR_INVALID, "spt_pfm_read: %s: bad header (width height scale)", path);
+    }
+    const size_t row = (size_t)w * 3, count = row * h;
+    float* out = (float*)std::malloc(sizeof(float) * count);
+    if (!out) {
+        std::fclose(f);
+        return spt_set_error(SPT_ERR_OOM, "spt_pfm_read: %s: %lu x %lu floats", path, w, h);
+    }
+    bool ok = true;
+    for (size_t y = 0; ok && y < h; y++)  // rows bottom-up in the file
+        ok = std::fread(out + (h - 1 - y) * row, sizeof(float), row, f) == row;
+    std::fclose(f);
+    if (!ok) {
+        std::free(out);
+        return spt_set_error(SPT_ERR_IO, "spt_pfm_read: %s: short file (%lu x %lu)", path, w, h);
+    }
+    if (scale > 0.0) {  // big endian
+        unsigned char* p = (unsigned char*)out;
+        for (size_t k = 0; k < count; k++, p += 4) {
+            const unsigned char a = p[0], b = p[1];
+            p[0] = p[3]; p[1] = p[2]; p[2] = b; p[3] = a;
+        }
+    }
+    *rgb = out;
+    *w_out = (uint32_t)w;
+    *h_out = (uint32_t)h;
+    return SPT_OK;
+}
+
+void spt_pfm_free(float* rgb) { std::free(rgb); }
+
+spt_status spt_envmap_from_latlong(const float* rgb, uint32_t w, uint32_t h, uint32_t n, float* out_rgb) {
+    static const char* what = "spt_envmap_from_latlong";
+    if (!rgb || !out_rgb) return spt_set_error(SPT_ERR_INVALID, "%s: NULL argument", what);
+    if (w == 0 || h == 0 || n == 0) return spt_set_error(SPT_ERR_INVALID, "%s: empty image (%u x %u -> %u)", what, w, h, n);
+    if (n > 4096) return spt_set_error(SPT_ERR_LIMIT, "%s: n = %u (at most 4096)", what, n);
+    if (w > (1u << 16) || h > (1u << 16)) return spt_set_error(SPT_ERR_LIMIT, "%s: %u x %u source (at most 65536 a side)", what, w, h);
+    const double pi = 3.14159265358979323846;
+    for (uint32_t j = 0; j < n; j++)
+        for (uint32_t i = 0; i < n; i++) {
+            // the texel centre's direction (the inverse of the lookup's fold)
+            const double a = ((double)i + 0.5) / (double)n * 2.0 - 1.0, b = ((double)j + 0.5) / (double)n * 2.0 - 1.0;
+            const double z = 1.0 - std::fabs(a) - std::fabs(b);
+            double x = a, y = b;
+            if (z < 0.0) {
+                x = (1.0 - std::fabs(b)) * (a < 0.0 ? -1.0 : 1.0);
+                y = (1.0 - std::fabs(a)) * (b < 0.0 ? -1.0 : 1.0);
+            }
+            const double len = std::sqrt(x * x + y * y + z * z);
+            double cz = z / len;
+            cz = cz < -1.0 ? -1.0 : (cz > 1.0 ? 1.0 : cz);
+            const double theta = std::acos(cz);
+            double phi = std::atan2(y, x);
+            if (phi < 0.0) phi += 2.0 * pi;
+            const double fx = phi / (2.0 * pi) * (double)w - 0.5, fy = theta / pi * (double)h - 0.5;
+            const double x0f = std::floor(fx), y0f = std::floor(fy);
+            const double dx = fx - x0f, dy = fy - y0f;
+            const long wl = (long)w, hl = (long)h;
+            const long x0 = (((long)x0f % wl) + wl) % wl, x1 = (x0 + 1) % wl;  // u wraps
+            long y0 = (long)y0f, y1 = y0 + 1;                                    // v clamps
+            y0 = y0 < 0 ? 0 : (y0 > hl - 1 ? hl - 1 : y0);
+            y1 = y1 < 0 ? 0 : (y1 > hl - 1 ? hl - 1 : y1);
+            for (int c = 0; c < 3; c++) {
+                const double t00 = rgb[((size_t)y0 * w + x0) * 3 + c], t10 = rgb[((size_t)y0 * w + x1) * 3 + c];
+                const double t01 = rgb[((size_t)y1 * w + x0) * 3 + c], t11 = rgb[((size_t)y1 * w + x1) * 3 + c];
+                const double top = (1.0 - dx) * t00 + dx * t10, bot = (1.0 - dx) * t01 + dx * t11;
+                out_rgb[((size_t)j * n + i) * 3 + c] = (float)((1.0 - dy) * top + dy * bot);
+            }
+        }
+    return SPT_OK;
 }
 
 }  // extern "C"

@@ -1105,9 +1105,16 @@ __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, cons
             // miss: film += select(!hit && active, contrib, 0)  (main.cpp:407)
             escaped = true;
             if (kMode != kModeUnit) {
-                lr = lr + tr * a.env_r;
-                lg = lg + tg * a.env_g;
-                lb = lb + tb * a.env_b;
+                float er = a.env_r, eg = a.env_g, eb = a.env_b;
+                if constexpr (kSpt) {
+                    if (a.sc.envmap) {  // the sky image in the ray's direction, tinted by env
+                        const V3 m = env_radiance(a.sc, v3(q2.x, q2.y, q2.z));
+                        er = er * m.x; eg = eg * m.y; eb = eb * m.z;
+                    }
+                }
+                lr = lr + tr * er;
+                lg = lg + tg * eg;
+                lb = lb + tb * eb;
             }
         } else {
             const bool bounce = depth + 1 < a.max_depth;
@@ -1393,7 +1400,11 @@ __global__ __launch_bounds__(kIsectBlock) void aov_kernel(AovArgs a) {
 //
 // kList (spt_render_accum_list, never with kDrain): a new path's work item runs
 // over the list_n listed pixels and its pixel is list[q] (refill_kernel).
-template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false>
+//
+// kEnv (albedo / emitter modes only): the scene has a sky image
+// (DeviceScene::envmap), looked up where a path escapes —
+// separate instances, so the others keep their registers and scratch.
+template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false>
 __global__ __launch_bounds__(kIsectBlock)
 __attribute__((amdgpu_waves_per_eu(kDrain && kMode == kModeUnit ? (kNt ? SPT_DRAIN_WAVES_NT : SPT_DRAIN_WAVES)
                                    : kDrain ? SPT_DRAIN_WAVES_RGB : SPT_FUSED_WAVES, 8)))
@@ -1486,9 +1497,14 @@ void render_fused_kernel(FusedArgs a) {
                 const bool sph = kMode != kModeUnit && slot < -1;
                 if (slot == -1) {
                     if (kMode != kModeUnit) {
-                        lr = lr + thr * a.env_r;                   // main.cpp:407
-                        lg = lg + thg * a.env_g;
-                        lb = lb + thb * a.env_b;
+                        float er = a.env_r, eg = a.env_g, eb = a.env_b;
+                        if constexpr (kEnv) {  // the sky image (shade_block)
+                            const V3 m = env_radiance(a.sc, dir);
+                            er = er * m.x; eg = eg * m.y; eb = eb * m.z;
+                        }
+                        lr = lr + thr * er;                        // main.cpp:407
+                        lg = lg + thg * eg;
+                        lb = lb + thb * eb;
                     }
                 } else {
                     const float4 m0 = sph ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : a.sc.snrm[(size_t)slot * 3];
@@ -2139,7 +2155,7 @@ static hipError_t launch_camera_cast_t(const CameraCastArgs& a, hipStream_t s) {
 
 template <typename Tr, bool kNt>
 static hipError_t launch_camera_cast_m(const CameraCastArgs& a, int mode, hipStream_t s) {
-    const bool spt = a.s.sc.nsph || a.s.sc.nkind;  // never in unit mode (launch_shade)
+    const bool spt = a.s.sc.nsph || a.s.sc.nkind || a.s.sc.envmap;  // never in unit mode (launch_shade)
     if (mode == kModeEmit && spt) return launch_camera_cast_t<Tr, kModeEmit, true, kNt>(a, s);
     if (mode == kModeEmit) return launch_camera_cast_t<Tr, kModeEmit, false, kNt>(a, s);
     if (mode == kModeAlbedo && spt) return launch_camera_cast_t<Tr, kModeAlbedo, true, kNt>(a, s);
@@ -2228,7 +2244,7 @@ hipError_t launch_isect_public(const IsectPublicArgs& a, hipStream_t s) {
 hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipStream_t s) {
     if (grid_items == 0) return hipSuccess;
     const dim3 g(blocks_for(grid_items, kShadeBlock)), b(kShadeBlock);
-    const bool spt = a.sc.nsph || a.sc.nkind;  // never in unit mode (spt_render)
+    const bool spt = a.sc.nsph || a.sc.nkind || a.sc.envmap;  // never in unit mode (spt_render)
     if (a.nt) {  // non-temporal queue accesses (spt_config.queue_cache), every instance
         if (mode == kModeEmit && spt) hipLaunchKernelGGL((shade_kernel<kModeEmit, true, true>), g, b, 0, s, a);
         else if (mode == kModeEmit) hipLaunchKernelGGL((shade_kernel<kModeEmit, false, true>), g, b, 0, s, a);
@@ -2245,7 +2261,7 @@ hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipSt
     return hipGetLastError();
 }
 
-template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false>
+template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false>
 static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
     static thread_local size_t cached_lds = 0;
     static thread_local uint32_t cached = 0;
@@ -2257,7 +2273,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     (void)hipGetDevice(&dev);
     if (!cached || cached_lds != lds || cached_dev != dev) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList>,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv>,
                                                          kIsectBlock, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -2270,15 +2286,23 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     // (the drain's grid cannot follow its count, which is on the device)
     const uint32_t blocks = kDrain ? scaled : min(scaled, blocks_for(a.count > 0 ? a.count : 1, kIsectBlock));
     if (lanes_out) *lanes_out = blocks * kIsectBlock;
-    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList>), dim3(blocks), dim3(kIsectBlock), lds, s, a);
+    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv>), dim3(blocks), dim3(kIsectBlock), lds, s, a);
     return hipGetLastError();
+}
+
+// a scene with a sky image takes the kEnv instance (never in unit mode, spt_render)
+template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false>
+static hipError_t launch_fused_e(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
+    if constexpr (kMode != kModeUnit)
+        if (a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true>(a, s, lanes_out);
+    return launch_fused_t<Tr, kMode, kDrain, kNt, kList>(a, s, lanes_out);
 }
 
 template <int kMode, bool kNt>
 static hipError_t launch_drain_m(const FusedArgs& a, hipStream_t s) {
-    if (a.sc.nodes8 && a.sc.node6) return launch_fused_t<Tracer6F, kMode, true, kNt>(a, s, nullptr);
-    if (a.sc.nodes8) return launch_fused_t<Tracer8F, kMode, true, kNt>(a, s, nullptr);
-    return launch_fused_t<Tracer, kMode, true, kNt>(a, s, nullptr);
+    if (a.sc.nodes8 && a.sc.node6) return launch_fused_e<Tracer6F, kMode, true, kNt>(a, s, nullptr);
+    if (a.sc.nodes8) return launch_fused_e<Tracer8F, kMode, true, kNt>(a, s, nullptr);
+    return launch_fused_e<Tracer, kMode, true, kNt>(a, s, nullptr);
 }
 
 // Sort key of a queued path (launch_drain_sort): its direction's octant, then
@@ -2348,9 +2372,9 @@ hipError_t launch_drain(const FusedArgs& a, int mode, hipStream_t s) {
 
 template <typename Tr>
 static hipError_t launch_fused_list(const FusedArgs& a, int mode, hipStream_t s, uint32_t* lanes_out) {
-    if (mode == kModeEmit) return launch_fused_t<Tr, kModeEmit, false, false, true>(a, s, lanes_out);
-    if (mode == kModeAlbedo) return launch_fused_t<Tr, kModeAlbedo, false, false, true>(a, s, lanes_out);
-    return launch_fused_t<Tr, kModeUnit, false, false, true>(a, s, lanes_out);
+    if (mode == kModeEmit) return launch_fused_e<Tr, kModeEmit, false, false, true>(a, s, lanes_out);
+    if (mode == kModeAlbedo) return launch_fused_e<Tr, kModeAlbedo, false, false, true>(a, s, lanes_out);
+    return launch_fused_e<Tr, kModeUnit, false, false, true>(a, s, lanes_out);
 }
 
 hipError_t launch_fused(const FusedArgs& a, int mode, hipStream_t s, uint32_t* lanes_out) {
@@ -2360,18 +2384,18 @@ hipError_t launch_fused(const FusedArgs& a, int mode, hipStream_t s, uint32_t* l
         return launch_fused_list<Tracer>(a, mode, s, lanes_out);
     }
     if (a.sc.nodes8 && a.sc.node6) {
-        if (mode == kModeEmit) return launch_fused_t<Tracer6F, kModeEmit>(a, s, lanes_out);
-        if (mode == kModeAlbedo) return launch_fused_t<Tracer6F, kModeAlbedo>(a, s, lanes_out);
-        return launch_fused_t<Tracer6F, kModeUnit>(a, s, lanes_out);
+        if (mode == kModeEmit) return launch_fused_e<Tracer6F, kModeEmit>(a, s, lanes_out);
+        if (mode == kModeAlbedo) return launch_fused_e<Tracer6F, kModeAlbedo>(a, s, lanes_out);
+        return launch_fused_e<Tracer6F, kModeUnit>(a, s, lanes_out);
     }
     if (a.sc.nodes8) {
-        if (mode == kModeEmit) return launch_fused_t<Tracer8F, kModeEmit>(a, s, lanes_out);
-        if (mode == kModeAlbedo) return launch_fused_t<Tracer8F, kModeAlbedo>(a, s, lanes_out);
-        return launch_fused_t<Tracer8F, kModeUnit>(a, s, lanes_out);
+        if (mode == kModeEmit) return launch_fused_e<Tracer8F, kModeEmit>(a, s, lanes_out);
+        if (mode == kModeAlbedo) return launch_fused_e<Tracer8F, kModeAlbedo>(a, s, lanes_out);
+        return launch_fused_e<Tracer8F, kModeUnit>(a, s, lanes_out);
     }
-    if (mode == kModeEmit) return launch_fused_t<Tracer, kModeEmit>(a, s, lanes_out);
-    if (mode == kModeAlbedo) return launch_fused_t<Tracer, kModeAlbedo>(a, s, lanes_out);
-    return launch_fused_t<Tracer, kModeUnit>(a, s, lanes_out);
+    if (mode == kModeEmit) return launch_fused_e<Tracer, kModeEmit>(a, s, lanes_out);
+    if (mode == kModeAlbedo) return launch_fused_e<Tracer, kModeAlbedo>(a, s, lanes_out);
+    return launch_fused_e<Tracer, kModeUnit>(a, s, lanes_out);
 }
 
 hipError_t launch_refill(const RefillArgs& a, uint32_t grid_items, hipStream_t s) {

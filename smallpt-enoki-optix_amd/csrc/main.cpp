@@ -22,6 +22,7 @@
 //                  [--gpus N] [--rows-per-group R] [--rehearse-shared-gpu]
 //                  [--aov PREFIX] [--denoise [--denoise-iters N]]
 //                  [--passes N] [--variance FILE] [--denoise-var]
+//                  [--envmap sky.pfm [--env-res N] | --envmap-oct sky.pfm] [--env-rotate-y DEG]
 //
 // --aov PREFIX writes the first-hit buffers of the render (spt_render_aov) as
 // PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm (depth in all three
@@ -37,11 +38,21 @@
 // that variance and the first-hit buffers as --denoise is (raw image to
 // <out>.raw.pfm; --denoise-iters applies); it implies the second moments.
 // Single-device too.
+//
+// --envmap FILE lights the scene with a lat-long sky image (a PFM, pbrt's
+// convention, z up), resampled to an --env-res N (default 512) octahedral map
+// (spt_envmap_from_latlong, spt_scene_set_envmap); --envmap-oct FILE takes a
+// square PFM that is octahedral already.  --env-rotate-y DEG turns the world
+// about its y axis before the lookup.  The map is set after --save-cache has
+// written its file (the cache does not store it), so the flags work with a
+// .sptc scene too, and with --passes, --adaptive, --aov and --denoise*.
+// Single-device.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -223,6 +234,10 @@ int main(int argc, char** argv) {
     spt_adapt_params ap;
     spt_default_adapt_params(&ap);
     std::string spp_map_out;
+    std::string envmap_in;      // --envmap (lat-long) or --envmap-oct
+    bool envmap_oct = false, env_rotate = false;
+    int env_res = 512;
+    double env_rotate_y = 0.0;  // degrees
     int denoise_iters = -1;  // -1: spt_default_denoise_params
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
@@ -259,6 +274,10 @@ int main(int argc, char** argv) {
         else if (a == "--min-spp") ap.min_spp = (uint32_t)std::atoi(next());
         else if (a == "--max-spp") ap.max_spp = (uint32_t)std::atoi(next());
         else if (a == "--spp-map") spp_map_out = next();
+        else if (a == "--envmap") { envmap_in = next(); envmap_oct = false; }
+        else if (a == "--envmap-oct") { envmap_in = next(); envmap_oct = true; }
+        else if (a == "--env-res") env_res = std::atoi(next());
+        else if (a == "--env-rotate-y") { env_rotate_y = std::atof(next()); env_rotate = true; }
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
     }
@@ -285,6 +304,14 @@ int main(int argc, char** argv) {
         std::cerr << "--adaptive takes TOL >= 0, --min-spp <= --max-spp < 2^24\n";
         return 2;
     }
+    if (envmap_in.empty() && env_rotate) {
+        std::cerr << "--env-rotate-y goes with --envmap / --envmap-oct\n";
+        return 2;
+    }
+    if (!envmap_in.empty() && (ngpu > 1 || env_res < 1 || env_res > 4096 || !std::isfinite(env_rotate_y))) {
+        std::cerr << "--envmap renders on one device (not with --gpus above 1); --env-res takes 1..4096\n";
+        return 2;
+    }
     if (do_denoise && do_denoise_var) {
         std::cerr << "--denoise and --denoise-var: choose one\n";
         return 2;
@@ -297,7 +324,7 @@ int main(int argc, char** argv) {
     const bool accum = passes > 0 || !variance_out.empty() || do_denoise_var || adaptive;
     const bool moments = !variance_out.empty() || do_denoise_var || adaptive;
     if (passes == 0) passes = 1;
-    if ((want_aov || accum) && ngpu == 1) ngpu = 0;  // one tile: the single-device path below (the same image)
+    if ((want_aov || accum || !envmap_in.empty()) && ngpu == 1) ngpu = 0;  // one tile: the single-device path below (the same image)
     try {
         const bool cache = spt::ends_with(obj, ".sptc");
         std::unique_ptr<spt::Mesh> mesh;
@@ -325,6 +352,18 @@ int main(int argc, char** argv) {
         if (!cache_out.empty()) {
             if (ngpu >= 1) throw std::runtime_error("--save-cache: use it without --gpus");
             scene.save(cache_out);
+        }
+        if (!envmap_in.empty()) {  // after the save: the cache does not store the map
+            const spt::PfmImage img(envmap_in);
+            const double t = env_rotate_y * 3.14159265358979323846 / 180.0, c = std::cos(t), sn = std::sin(t);
+            const float rot[9] = {(float)c, 0.0f, (float)sn, 0.0f, 1.0f, 0.0f, (float)-sn, 0.0f, (float)c};
+            if (envmap_oct) {
+                if (img.w != img.h) throw std::runtime_error("--envmap-oct: " + envmap_in + " is not square");
+                scene.set_envmap(img.rgb, img.w, env_rotate ? rot : nullptr);
+            } else {
+                const std::vector<float> oct = spt::envmap_from_latlong(img.rgb, img.w, img.h, (uint32_t)env_res);
+                scene.set_envmap(oct.data(), (uint32_t)env_res, env_rotate ? rot : nullptr);
+            }
         }
         if (pi.has_camera) {
             p.camera = pi.camera;

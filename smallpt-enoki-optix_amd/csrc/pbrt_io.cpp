@@ -18,7 +18,9 @@
 //              ("float scale") becomes the emission of the shapes under it
 //   camera     Camera "perspective" "float fov" with the CTM at that point,
 //              Film "xresolution"/"yresolution"
-//   sky        LightSource "infinite" "rgb L" (constant radiance)
+//   sky        LightSource "infinite" "rgb L" (constant radiance); a "string
+//              mapname" image is not read: the light keeps its constant L
+//              (set a sky image with spt_scene_set_envmap, include/spt.h)
 //   Include    relative to the including file
 //
 // The output is the same spt_mesh the OBJ reader returns (material 0 is the

@@ -725,7 +725,8 @@ RenderPlanIn plan_inputs(const spt_scene_t* sc, const spt_render_params& p, uint
     in.cfg = &sc->cfg;
     // What a path carries (spt_internal.h PathMode): the reference's case
     // (every albedo 1, no emitters) needs only the ray and an escaped flag.
-    const bool unit = sc->albedo_unit && sc->ntex == 0 && sc->nsph == 0 && sc->nkind == 0;
+    // (a sky image needs radiance in the film slots: an escaped flag cannot carry it)
+    const bool unit = sc->albedo_unit && sc->ntex == 0 && sc->nsph == 0 && sc->nkind == 0 && !sc->envmap;
     in.mode = sc->emission ? kModeEmit : (unit ? kModeUnit : kModeAlbedo);
     in.planes = mode_planes(in.mode);
     in.film_unit = mode_film_bytes(in.mode);

@@ -297,6 +297,9 @@ spt_status spt_scene_save(spt_scene sc, const char* path, const void* extra, uin
     if (extra_bytes && !extra) return fail(SPT_ERR_INVALID, "%s: extra is NULL with %llu bytes", what,
                                            (unsigned long long)extra_bytes);
     std::lock_guard<std::mutex> lk(sc->mu);
+    if (sc->envmap)  // the format has no section for it yet: refuse rather than drop the sky silently
+        return fail(SPT_ERR_INVALID, "%s: the scene holds an environment map, which the cache does not store "
+                    "(remove it with spt_scene_set_envmap(scene, NULL, 0, NULL), save, and set it again after loading)", what);
     CacheHeader h;
     std::memset(&h, 0, sizeof(h));
     std::memcpy(h.magic, kCacheMagic, 8);

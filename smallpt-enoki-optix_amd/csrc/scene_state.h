@@ -88,6 +88,9 @@ struct spt_scene_t {
     uint32_t nsph = 0;
     uint32_t* mat_kind = nullptr;  // SPT_MAT_* per material (spt_scene_set_material_kinds)
     uint32_t nkind = 0;
+    // the sky image (spt_scene_set_envmap): the device struct and the texels behind it
+    spt::DeviceEnvMap* envmap = nullptr;
+    float4* env_texels = nullptr;
     uint64_t node_bytes = 0;  // bytes behind nodes / nodes8 (spt_scene_save)
     uint32_t stack_depth = 1;
     spt_scene_stats stats{};
@@ -107,6 +110,7 @@ struct spt_scene_t {
         d.tex_info = tex_info; d.ntex = ntex; d.texels = texels;
         d.spheres = spheres; d.sph_mat = sph_mat; d.nsph = nsph;
         d.mat_kind = mat_kind; d.nkind = nkind;
+        d.envmap = envmap;
         return d;
     }
     void release() {
@@ -115,6 +119,7 @@ struct spt_scene_t {
         spt::workspace_release(ws);
         spt::hfree(nodes); spt::hfree(nodes8); spt::hfree(emission); spt::hfree(tris); spt::hfree(snrm); spt::hfree(tc); spt::hfree(orig2slot); spt::hfree(albedo);
         spt::hfree(tex_info); spt::hfree(texels); spt::hfree(spheres); spt::hfree(sph_mat); spt::hfree(mat_kind);
+        spt::hfree(envmap); spt::hfree(env_texels);
         spt::refit_plan_release(refit);
         spt::hfree(refit_bad);
     }

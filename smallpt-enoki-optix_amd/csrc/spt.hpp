@@ -115,6 +115,12 @@ class Scene {
         check(spt_scene_update_geometry_device(scene_, pos_tri, pos, nvert, ntri, nrm_tri, nrm, nnrm, stream),
               "spt_scene_update_geometry_device");
     }
+    // spt_scene_set_envmap: the octahedral sky image (n x n interleaved RGB; see
+    // envmap_from_latlong) and its world -> map rotation (9 floats row-major,
+    // nullptr: identity); rgb nullptr removes the map
+    void set_envmap(const float* rgb, uint32_t n, const float* rotation = nullptr) {
+        check(spt_scene_set_envmap(scene_, rgb, n, rotation), "spt_scene_set_envmap");
+    }
     spt_refit_stats refit_stats() const {
         spt_refit_stats st{};
         check(spt_scene_get_refit_stats(scene_, &st), "spt_scene_get_refit_stats");
@@ -139,6 +145,23 @@ class Scene {
     spt_pbrt_info pbrt_{};
     spt_scene scene_ = nullptr;
 };
+
+// A PFM image on the host (spt_pfm_read): w x h interleaved RGB, rows top-down.
+struct PfmImage {
+    float* rgb = nullptr;
+    uint32_t w = 0, h = 0;
+    explicit PfmImage(const std::string& path) { check(spt_pfm_read(path.c_str(), &rgb, &w, &h), "spt_pfm_read"); }
+    ~PfmImage() { spt_pfm_free(rgb); }
+    PfmImage(const PfmImage&) = delete;
+    PfmImage& operator=(const PfmImage&) = delete;
+};
+
+// spt_envmap_from_latlong: a lat-long image resampled to n x n octahedral texels (host only).
+inline std::vector<float> envmap_from_latlong(const float* rgb, uint32_t w, uint32_t h, uint32_t n) {
+    std::vector<float> out((size_t)n * n * 3);
+    check(spt_envmap_from_latlong(rgb, w, h, n, out.data()), "spt_envmap_from_latlong");
+    return out;
+}
 
 // Device floats owned for a scope (hipMalloc / hipFree; throws like check()).
 class DeviceFloats {

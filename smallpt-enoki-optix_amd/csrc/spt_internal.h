@@ -75,6 +75,8 @@ struct PathQueue {
     float2* rad;
 };
 
+struct DeviceEnvMap;
+
 // Geometry on device, leaf ("slot") order.
 struct DeviceScene {
     const float4* nodes;   // BVH2: 4 per node (bvh_build.h)
@@ -99,7 +101,64 @@ struct DeviceScene {
     uint32_t nsph;
     const uint32_t* mat_kind;  // per material SPT_MAT_* (null: every material diffuse)
     uint32_t nkind;
+    const DeviceEnvMap* envmap;  // the sky image (spt_scene_set_envmap; null: the constant params.env)
 };
+
+// The environment map on the device: an octahedral image of
+// n x n RGB texels inside a one-texel gutter, so texel (i, j), i and j in
+// [-1, n], is texels[(j + 1) * (n + 2) + (i + 1)].  The gutter holds the texel
+// across the octahedral edge (envmap_wrap), filled when the map is set, so the
+// lookup is a plain bilinear fetch.  One pointer in DeviceScene: the kernel
+// arguments do not grow by the rotation.
+struct DeviceEnvMap {
+    uint32_t n;
+    float rot[9];          // row-major, world -> map
+    const float4* texels;  // (n + 2)^2, w unused
+};
+constexpr uint32_t kEnvMapMaxN = 4096;
+
+// Texel (i, j) with i, j in [-1, n] -> the texel inside [0, n)^2 it stands
+// for: the column is wrapped first, then the row.  An edge is mirrored about
+// its midpoint; a corner's diagonal neighbour is the opposite corner.
+SPT_HD void envmap_wrap(int32_t n, int32_t& i, int32_t& j) {
+    if (i < 0) { i = 0; j = n - 1 - j; }
+    else if (i >= n) { i = n - 1; j = n - 1 - j; }
+    if (j < 0) { j = 0; i = n - 1 - i; }
+    else if (j >= n) { j = n - 1; i = n - 1 - i; }
+}
+
+// Radiance of the map in direction d (any length, as traced), f32 with every
+// operation rounded and in this order: tests/envmap_ref.py restates it.
+SPT_HD V3 env_radiance(const DeviceScene& sc, V3 d) {
+    const DeviceEnvMap& m = *sc.envmap;
+    const float ex = (m.rot[0] * d.x + m.rot[1] * d.y) + m.rot[2] * d.z;
+    const float ey = (m.rot[3] * d.x + m.rot[4] * d.y) + m.rot[5] * d.z;
+    const float ez = (m.rot[6] * d.x + m.rot[7] * d.y) + m.rot[8] * d.z;
+    const float s = (fabsf(ex) + fabsf(ey)) + fabsf(ez);
+    if (!(s > 0.0f && s < INFINITY)) return v3(0.0f, 0.0f, 0.0f);
+    float a = ex / s, b = ey / s;
+    if (ez < 0.0f) {  // the lower hemisphere folds over the diamond's edges
+        const float fa = (1.0f - fabsf(b)) * (a < 0.0f ? -1.0f : 1.0f);
+        const float fb = (1.0f - fabsf(a)) * (b < 0.0f ? -1.0f : 1.0f);
+        a = fa;
+        b = fb;
+    }
+    const float fn = (float)m.n;
+    const float fx = (a * 0.5f + 0.5f) * fn - 0.5f, fy = (b * 0.5f + 0.5f) * fn - 0.5f;
+    const float fi = floorf(fx), fj = floorf(fy);
+    const float wx = fx - fi, wy = fy - fj;
+    // |a|, |b| <= 1 puts both in [-1, n - 1]; the clamp keeps any input inside the array
+    const int32_t hi = (int32_t)m.n - 1;
+    const int32_t i0 = (int32_t)fi < -1 ? -1 : ((int32_t)fi > hi ? hi : (int32_t)fi);
+    const int32_t j0 = (int32_t)fj < -1 ? -1 : ((int32_t)fj > hi ? hi : (int32_t)fj);
+    const size_t pitch = (size_t)m.n + 2u;
+    const float4* t = m.texels + (size_t)(j0 + 1) * pitch + (size_t)(i0 + 1);
+    const float4 t00 = t[0], t10 = t[1], t01 = t[pitch], t11 = t[pitch + 1];
+    const float ux = 1.0f - wx, uy = 1.0f - wy;
+    const V3 top = v3(ux * t00.x + wx * t10.x, ux * t00.y + wx * t10.y, ux * t00.z + wx * t10.z);
+    const V3 bot = v3(ux * t01.x + wx * t11.x, ux * t01.y + wx * t11.y, ux * t01.z + wx * t11.z);
+    return v3(uy * top.x + wy * bot.x, uy * top.y + wy * bot.y, uy * top.z + wy * bot.z);
+}
 
 constexpr uint32_t kMatDiffuse = 0, kMatMirror = 1, kMatGlass = 2;  // SPT_MAT_*
 SPT_HD uint32_t material_kind(const DeviceScene& sc, uint32_t mat) {

@@ -42,6 +42,7 @@ EXPORTED = [
     "spt_render_accum", "spt_render_accum_async",
     "spt_default_denoise_var_params", "spt_denoise_var_scratch_bytes", "spt_denoise_var",
     "spt_default_adapt_params", "spt_adapt_select_scratch_bytes", "spt_adapt_select", "spt_render_accum_list",
+    "spt_scene_set_envmap", "spt_envmap_from_latlong", "spt_pfm_read", "spt_pfm_free",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -266,6 +267,10 @@ def _load() -> ctypes.CDLL:
         "spt_adapt_select": (i32, [POINTER(AdaptParams), u32, u32, vp, vp, vp, vp, POINTER(u32), vp, vp]),
         "spt_render_accum_list": (i32, [vp, POINTER(RenderParams), POINTER(Accum), POINTER(PixelList),
                                         POINTER(RenderStats), vp]),
+        "spt_scene_set_envmap": (i32, [vp, vp, u32, vp]),
+        "spt_envmap_from_latlong": (i32, [vp, u32, u32, u32, vp]),
+        "spt_pfm_read": (i32, [c_char_p, POINTER(POINTER(ctypes.c_float)), POINTER(u32), POINTER(u32)]),
+        "spt_pfm_free": (None, [POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -216,6 +216,20 @@ class HipBackend:
         k = np.ascontiguousarray(np.asarray(kinds, dtype=np.uint32).reshape(-1))
         check(lib.spt_scene_set_material_kinds(self._scene, k.ctypes.data, k.size), "spt_scene_set_material_kinds")
 
+    def set_envmap(self, image=None, rotation=None) -> None:
+        """spt_scene_set_envmap: the octahedral sky image, (N, N, 3) float32 (row = b,
+        column = a; envmap_from_latlong makes one from a lat-long image), and a
+        3 x 3 world -> map rotation (None: identity).  image None removes the map."""
+        if image is None:
+            check(lib.spt_scene_set_envmap(self._scene, None, 0, None), "spt_scene_set_envmap")
+            return
+        img = np.ascontiguousarray(np.asarray(image, dtype=np.float32))
+        if img.ndim != 3 or img.shape[0] != img.shape[1] or img.shape[2] != 3:
+            raise ValueError(f"set_envmap: the image must be (N, N, 3), got {img.shape}")
+        rot = None if rotation is None else np.ascontiguousarray(np.asarray(rotation, dtype=np.float32).reshape(9))
+        check(lib.spt_scene_set_envmap(self._scene, img.ctypes.data, img.shape[0], _host_ptr(rot)),
+              "spt_scene_set_envmap")
+
     def set_texture(self, material: int, image=None) -> None:
         """Material `material`'s reflectance image (ImageTexture, main.cpp:34-80):
         (H, W, 3) float32, or None to remove it."""
@@ -867,3 +881,26 @@ def write_pfm(path: str, film: np.ndarray) -> None:
     _, h, w = f.shape
     check(lib.spt_pfm_write(path.encode(), f[0].ctypes.data, f[1].ctypes.data, f[2].ctypes.data, w, h),
           "spt_pfm_write")
+
+
+def read_pfm(path: str) -> np.ndarray:
+    """spt_pfm_read: a 3-channel PFM of either endianness as an (H, W, 3) float32
+    array, rows top-down (write_pfm(path, x) then read_pfm(path) gives x.transpose(1, 2, 0))."""
+    p, w, h = ctypes.POINTER(ctypes.c_float)(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib.spt_pfm_read(os.fsencode(path), ctypes.byref(p), ctypes.byref(w), ctypes.byref(h)), "spt_pfm_read")
+    try:
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).copy()
+    finally:
+        lib.spt_pfm_free(p)
+
+
+def envmap_from_latlong(img, n: int) -> np.ndarray:
+    """spt_envmap_from_latlong: an (H, W, 3) lat-long image (pbrt's convention, z up)
+    resampled to the (n, n, 3) octahedral image HipBackend.set_envmap takes.  Host only."""
+    src = np.ascontiguousarray(np.asarray(img, dtype=np.float32))
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError(f"envmap_from_latlong: the image must be (H, W, 3), got {src.shape}")
+    out = np.empty((max(int(n), 0), max(int(n), 0), 3), np.float32)
+    check(lib.spt_envmap_from_latlong(src.ctypes.data, src.shape[1], src.shape[0], int(n), out.ctypes.data),
+          "spt_envmap_from_latlong")
+    return out
