@@ -83,7 +83,11 @@ enum {
                                       drain (neither flag: spt_config.pipeline; AUTO = fused iff
                                       the tile has at most fused_max_paths paths, 2^20 by default,
                                       or at most wavefront_paths when that is set) */
-    SPT_FLAG_TIMING_ALL = 16u      /* with SPT_FLAG_TIMING: also shade / refill / resolve launches */
+    SPT_FLAG_TIMING_ALL = 16u,     /* with SPT_FLAG_TIMING: also shade / refill / resolve launches */
+    SPT_FLAG_NO_BOUNCE_CULL = 32u  /* the camera-cast kernel (spt_config.lockstep_first = 3) queues every
+                                      bounce ray: without it a bounce ray that misses every child of the
+                                      BVH root ends there (spt_render_stats.culled_paths) instead of in
+                                      the drain.  The image and the work counters do not depend on it */
 };
 
 /* The render loop of main.cpp:354-429 plus the tile/wavefront knobs. */
@@ -153,6 +157,11 @@ typedef struct spt_render_stats {
                                    the paths in flight (device memory taken by someone else) */
     uint32_t drain_refill_idle; /* wavefront: the drain's refill threshold that ran
                                    (spt_config.drain_refill_idle or its AUTO choice; 0: no drain) */
+    uint32_t culled_paths;      /* wavefront: bounce rays the camera-cast kernel ended at the BVH root (they
+                                   miss every child of it: the drain's first step would end them the same
+                                   way), counted in ray_casts and continuations, not in drained_paths,
+                                   drained_casts or lockstep_casts (SPT_FLAG_NO_BOUNCE_CULL: 0); saturates
+                                   at 2^32 - 1 (the struct's former tail padding: its size is unchanged) */
 } spt_render_stats;
 
 typedef struct spt_scene_stats {
@@ -328,7 +337,10 @@ typedef struct spt_config {
                                        same with its survivors compacted per XCD shard and the
                                        drain's per-XCD pools over those segments (one queue counter
                                        takes ~88 atomics per us; config 1 +11 % over 1, a single
-                                       render +18 %); 0: the persistent isect kernel
+                                       render +18 %) and, in unit mode on scenes below
+                                       256 MiB, its bounce rays that miss every child of the BVH
+                                       root ended there (SPT_FLAG_NO_BOUNCE_CULL: not; config 1
+                                       +1.8 %); 0: the persistent isect kernel
                                        for every cast.  Wide-BVH scenes (2 and 3; BVH2 scenes run
                                        1).  The image does not depend on it                 [0..3] */
     uint32_t fit_chunks;            /* 1: a job of more than fit_paths paths whose tile has at most

@@ -430,9 +430,51 @@ struct Tracer8T {
         return r == 0 ? o : (r == 1 ? v3(o.y, o.z, o.x) : v3(o.z, o.x, o.y));
     }
 
+    // The part of a ray's set-up the node visits read (visit_words6 /
+    // visit_words): the origin, the reciprocal direction, the octant in every
+    // byte of oct_rep, the box bound and the hit distance.  No Woop divide,
+    // nothing in LDS.  k: the Woop axis word (WoopRay::k), whose kz picks the
+    // triangle records' rotation kept in oct_rep; a caller that tests no
+    // triangle passes kNoRot.  The traversal starts at the root (nhits).
+    static constexpr uint32_t kNoRot = 2u << 4;
+    __device__ __forceinline__ void init_slabs(V3 o_, V3 d, float tmin_, float tmax_, uint32_t k) {
+        o = o_;
+        const float dx = fabsf(d.x) < kMinDir ? copysignf(kMinDir, d.x) : d.x;
+        const float dy = fabsf(d.y) < kMinDir ? copysignf(kMinDir, d.y) : d.y;
+        const float dz = fabsf(d.z) < kMinDir ? copysignf(kMinDir, d.z) : d.z;
+        // hardware reciprocal (<= 1 ulp): the slab margins (kMarginRel) absorb
+        // it, and the triangle test keeps its own correctly rounded divides
+        ix = __builtin_amdgcn_rcpf(dx); iy = __builtin_amdgcn_rcpf(dy); iz = __builtin_amdgcn_rcpf(dz);
+        const uint32_t oct = (ix < 0.0f ? 1u : 0u) | (iy < 0.0f ? 2u : 0u) | (iz < 0.0f ? 4u : 0u);
+        const uint32_t oct_inv = oct ^ 7u;
+        const uint32_t kz = k >> 4;  // rotation r = (kz + 1) mod 3 puts kz last
+        oct_rep = oct_inv * 0x01010101u | ((kz == 2u ? 0u : kz + 1u) << 3);
+        tmin = tmin_;
+        tbox = box_tmin(tmin_);
+        nhits = 1u << (24u + oct_inv);  // the root: slot 0 of a virtual group at node 0
+        ht = tmax_;
+    }
+
+    // Whether the ray set up by init_slabs misses every child of the root: the
+    // visit step() makes first (node 0, nothing hit yet, ht = tmax), so a ray
+    // this answers true for ends in step()'s first call with no hit.  Node 0's
+    // address is wave-uniform.  Not for an empty scene (no node 0), and the
+    // caller must have no analytic spheres to test after the BVH.
+    __device__ __forceinline__ bool root_misses(const DeviceScene& sc) {
+        nhits = 0;
+        tbase = 0;
+        thits = 0;
+        tbase2 = 0;
+        thits2 = 0;
+        const uint4* np = sc.nodes8;
+        const uint4 w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3];
+        if constexpr (kW == 6) visit_words6(w0, w1, w2, w3);
+        else visit_words(w0, w1, w2, w3, np[4]);
+        return !(thits | (nhits & 0xff000000u));
+    }
+
     __device__ __forceinline__ void init(const DeviceScene& sc, V3 o_, V3 d, float tmin_, float tmax_, bool anyhit_,
                                          const Lds& L) {
-        o = o_;
         wr = woop_setup(o_, d);
         spa = (L.wbase + lane_id()) * 4u;
         *wrec(sc, L) = make_uint4(f2u(wr.Sx), f2u(wr.Sy), f2u(wr.Sz), wr.k);
@@ -442,26 +484,13 @@ struct Tracer8T {
         asm volatile("v_mov_b32 %0, -1" : "=v"(none));
         asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
         *hrec(sc, L) = make_uint4(none, none, zero, zero);
-        const float dx = fabsf(d.x) < kMinDir ? copysignf(kMinDir, d.x) : d.x;
-        const float dy = fabsf(d.y) < kMinDir ? copysignf(kMinDir, d.y) : d.y;
-        const float dz = fabsf(d.z) < kMinDir ? copysignf(kMinDir, d.z) : d.z;
-        // hardware reciprocal (<= 1 ulp): the slab margins (kMarginRel) absorb
-        // it, and the triangle test keeps its own correctly rounded divides
-        ix = __builtin_amdgcn_rcpf(dx); iy = __builtin_amdgcn_rcpf(dy); iz = __builtin_amdgcn_rcpf(dz);
-        const uint32_t oct = (ix < 0.0f ? 1u : 0u) | (iy < 0.0f ? 2u : 0u) | (iz < 0.0f ? 4u : 0u);
-        const uint32_t oct_inv = oct ^ 7u;
-        const uint32_t kz = wr.k >> 4;  // rotation r = (kz + 1) mod 3 puts kz last
-        oct_rep = oct_inv * 0x01010101u | ((kz == 2u ? 0u : kz + 1u) << 3);
-        tmin = tmin_;
-        tbox = box_tmin(tmin_);
+        init_slabs(o_, d, tmin_, tmax_, wr.k);
         anyhit = anyhit_;
-        nhits = 1u << (24u + oct_inv);  // the root: slot 0 of a virtual group at node 0
         tbase = 0;
         thits = 0;
         tbase2 = 0;
         thits2 = 0;
         done = sc.empty != 0;
-        ht = tmax_;
     }
 
     // inner children's meta bytes 0b001_11sss (24 + slot) take the ray's
@@ -1052,8 +1081,54 @@ struct QueueSrc {  // shade_kernel: queue slot i of a.in and its hit record
     __device__ __forceinline__ float4 q0() const { return ldq<kNt>(a.in.q0 + i); }
     __device__ __forceinline__ float2 rad() const { return ldq2<kNt>(a.in.rad + i); }
 };
-template <int kMode, bool kSpt, bool kNt, uint32_t kBlock, typename Src>
-__device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, const Src& src) {
+// shade_block's compaction: wave ballot + mbcnt rank, one queue atomic per
+// block.  Returns the lane's rank among its wave's survivors; base (thread 0
+// only): the block's first slot of the out queue, once the atomic returns.
+// (Casts and continuations are the queue counts: the refill that follows
+// adds them to the stats, so no per-block stats atomics contend here.)
+template <uint32_t kBlock>
+__device__ __forceinline__ uint32_t compact_block(const ShadeArgs& a, bool emit, uint32_t* s_wave_cnt, uint32_t tid,
+                                                  uint32_t lane, uint32_t wave, uint32_t& base) {
+    const uint64_t ball = __ballot(emit);
+    const uint32_t rank =
+        __builtin_amdgcn_mbcnt_hi((uint32_t)(ball >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ball, 0u));
+    if (lane == 0) s_wave_cnt[wave] = (uint32_t)__popcll(ball);
+    __syncthreads();
+    uint32_t total = 0;
+    if (tid == 0) {
+        for (uint32_t w = 0; w < kBlock / 64; w++) total += s_wave_cnt[w];
+        // returns during phase 2.  The address goes through an opaque VGPR
+        // zero: for a uniform address the compiler's atomic optimizer wraps
+        // the add in a wave scan whose readfirstlane waits for the return
+        // right here, serialising the atomic's latency with phase 2.
+        uint32_t zero;
+        asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+        if (a.shard_items) {  // the block's shard: its XCD's counter and segment (shard_base)
+            const uint32_t j = blockIdx.x % kShards;
+            if (total) base = atomicAdd(a.count_out + j * kShardStride + zero, total);
+            base += shard_base(j, a.shard_items, kBlock);
+        } else if (total) {
+            base = atomicAdd(a.count_out + zero, total);
+        }
+    }
+    return rank;
+}
+// shade_block's CullTr (camera_cast_cull_kernel only; void: none): the tracer
+// whose root visit every survivor's bounce ray takes right after phase 2 made
+// it.  A ray that misses every child of the root would end in the
+// drain's first trace step with no hit — after a queue entry written and read,
+// a lane of a shade-and-refill pass and a correctly rounded Woop set-up — so
+// it ends here instead: its escaped flag is written, it is not queued, and the
+// block adds it to culled[blockIdx.x % kShards] (one 128-B line per shard;
+// the host counts it as a cast and a continuation, render.cpp).  The
+// compaction then counts the survivors after the cull (no holes in the queue
+// or its segments), so the queue atomic follows phase 2 instead of hiding
+// behind it.  Same visit, same inputs as the drain's: the same bits.
+template <int kMode, bool kSpt, bool kNt, uint32_t kBlock, typename Src, typename CullTr = void>
+__device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, const Src& src,
+                                            unsigned long long* culled = nullptr) {
+    constexpr bool kCull = !std::is_void<CullTr>::value;
+    static_assert(!kCull || (kMode == kModeUnit && !kSpt), "the cull: unit mode, no analytic spheres");
     __shared__ uint32_t s_wave_cnt[kBlock / 64];
     __shared__ uint32_t s_wave_off[kBlock / 64];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -1176,31 +1251,9 @@ __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, cons
         }
     }
 
-    // ---- compaction: wave ballot + mbcnt rank, one queue atomic per block.
-    // (Casts and continuations are the queue counts: the refill that follows
-    // adds them to the stats, so no per-block stats atomics contend here.)
-    const uint64_t ball = __ballot(emit);
-    const uint32_t rank =
-        __builtin_amdgcn_mbcnt_hi((uint32_t)(ball >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ball, 0u));
-    if (lane == 0) s_wave_cnt[wave] = (uint32_t)__popcll(ball);
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-    if (tid == 0) {
-        for (uint32_t w = 0; w < kBlock / 64; w++) total += s_wave_cnt[w];
-        // returns during phase 2.  The address goes through an opaque VGPR
-        // zero: for a uniform address the compiler's atomic optimizer wraps
-        // the add in a wave scan whose readfirstlane waits for the return
-        // right here, serialising the atomic's latency with phase 2.
-        uint32_t zero;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
-        if (a.shard_items) {  // the block's shard: its XCD's counter and segment (shard_base)
-            const uint32_t j = blockIdx.x % kShards;
-            if (total) base = atomicAdd(a.count_out + j * kShardStride + zero, total);
-            base += shard_base(j, a.shard_items, kBlock);
-        } else if (total) {
-            base = atomicAdd(a.count_out + zero, total);
-        }
-    }
+    // ---- compaction (compact_block; the cull instances: after phase 2 and the cull)
+    uint32_t rank = 0, base = 0;
+    if constexpr (!kCull) rank = compact_block<kBlock>(a, emit, s_wave_cnt, tid, lane, wave, base);
 
     // ---- phase 2: the bounce ray of every survivor
     V3 no, nd;
@@ -1225,6 +1278,29 @@ __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, cons
             nd = scatter(a.sc, kind, slot, d, no, sn, xi_x, xi_y, wgt);
             tr = tr * wgt; tg = tg * wgt; tb = tb * wgt;
         }
+    }
+    if constexpr (kCull) {
+        // ---- the cull: the drain's first trace step of (no, nd), its root visit
+        __shared__ uint32_t s_wave_cull[kBlock / 64];
+        bool gone = false;
+        if (emit) {
+            CullTr ct;
+            ct.init_slabs(no, nd, kRayTmin, kRayTmax, CullTr::kNoRot);
+            gone = ct.root_misses(a.sc);
+            emit = !gone;
+        }
+        const uint64_t gball = __ballot(gone);
+        if (lane == 0) s_wave_cull[wave] = (uint32_t)__popcll(gball);
+        // (its barrier also publishes s_wave_cull)
+        rank = compact_block<kBlock>(a, emit, s_wave_cnt, tid, lane, wave, base);
+        if (tid == 0) {
+            uint32_t n = 0;
+            for (uint32_t w = 0; w < kBlock / 64; w++) n += s_wave_cull[w];
+            if (n) atomicAdd(culled + (blockIdx.x % kShards) * kCullStride, (unsigned long long)n);
+        }
+        // the path escaped: the drain's miss branch (unit mode: the flag byte)
+        if (gone)
+            a.sflag[film_slot((meta >> kMetaDepthBits) - a.sample0, pix, a.P, a.chunk_ns, a.work_order)] = 1;
     }
     if (tid == 0) {
         uint32_t off = base;
@@ -1269,10 +1345,11 @@ struct CamSrc {  // the path in registers: its first cast, just traced
     __device__ __forceinline__ float4 q0() const { return make_float4(1.0f, 1.0f, 1.0f, 0.0f); }  // main.cpp:391
     __device__ __forceinline__ float2 rad() const { return make_float2(0.0f, 0.0f); }
 };
-template <typename Tr, int kMode, bool kSpt, bool kNt, bool kList = false>
-__global__ __launch_bounds__(kIsectBlock) __attribute__((amdgpu_waves_per_eu(Tr::kMinWaves, 8)))
-void camera_cast_kernel(CameraCastArgs a) {
-    extern __shared__ uint32_t lds_stack[];
+// The body of both kernels below.  kCull (unit mode; culled: the per-shard
+// counters): a bounce ray that misses every child of the root ends here, not
+// in the drain (shade_block's CullTr).
+template <typename Tr, int kMode, bool kSpt, bool kNt, bool kList, bool kCull>
+__device__ __forceinline__ void camera_cast(const CameraCastArgs& a, uint32_t* lds_stack, unsigned long long* culled) {
     const Lds L = block_lds(lds_stack);
     const uint32_t i = blockIdx.x * kIsectBlock + threadIdx.x;
     const bool valid = i < a.n;
@@ -1294,7 +1371,22 @@ void camera_cast_kernel(CameraCastArgs a) {
             }
         c.h = tr.hit(a.s.sc, L);
     }
-    shade_block<kMode, kSpt, kNt, kIsectBlock>(a.s, valid, c);
+    if constexpr (kCull) shade_block<kMode, kSpt, kNt, kIsectBlock, CamSrc, Tr>(a.s, valid, c, culled);
+    else shade_block<kMode, kSpt, kNt, kIsectBlock>(a.s, valid, c);
+}
+template <typename Tr, int kMode, bool kSpt, bool kNt, bool kList = false>
+__global__ __launch_bounds__(kIsectBlock) __attribute__((amdgpu_waves_per_eu(Tr::kMinWaves, 8)))
+void camera_cast_kernel(CameraCastArgs a) {
+    extern __shared__ uint32_t lds_stack[];
+    camera_cast<Tr, kMode, kSpt, kNt, kList, false>(a, lds_stack, nullptr);
+}
+// ... with the bounce cull (unit mode, a non-empty scene without analytic
+// spheres): block b adds its culled paths to culled[(b % kShards) * kCullStride]
+template <typename Tr, bool kNt, bool kList>
+__global__ __launch_bounds__(kIsectBlock) __attribute__((amdgpu_waves_per_eu(Tr::kMinWaves, 8)))
+void camera_cast_cull_kernel(CameraCastArgs a, unsigned long long* culled) {
+    extern __shared__ uint32_t lds_stack[];
+    camera_cast<Tr, kModeUnit, false, kNt, kList, true>(a, lds_stack, culled);
 }
 
 // ------------------------------------------------------- first-hit buffers
@@ -2163,10 +2255,28 @@ static hipError_t launch_camera_cast_m(const CameraCastArgs& a, int mode, hipStr
     return launch_camera_cast_t<Tr, kModeUnit, false, kNt>(a, s);
 }
 
+// the bounce cull (RenderPlan::bounce_cull): unit mode only
+template <typename Tr, bool kNt>
+static hipError_t launch_camera_cast_cull_t(const CameraCastArgs& a, unsigned long long* culled, hipStream_t s) {
+    const size_t lds = (size_t)a.s.sc.stack_depth * Tr::kStackWords * kIsectBlock * sizeof(uint32_t) + Tr::kExtraLds;
+    const dim3 g(blocks_for(a.n, kIsectBlock)), b(kIsectBlock);
+    if (a.r.list) hipLaunchKernelGGL((camera_cast_cull_kernel<Tr, kNt, true>), g, b, lds, s, a, culled);
+    else hipLaunchKernelGGL((camera_cast_cull_kernel<Tr, kNt, false>), g, b, lds, s, a, culled);
+    return hipGetLastError();
+}
+
 // wide-BVH scenes only (camera_cast_supported); a.n: the work items, known exactly
-hipError_t launch_camera_cast(const CameraCastArgs& a, int mode, hipStream_t s) {
+hipError_t launch_camera_cast(const CameraCastArgs& a, int mode, hipStream_t s, unsigned long long* culled) {
     if (a.n == 0) return hipSuccess;
     if (!a.s.sc.nodes8) return hipErrorInvalidValue;
+    if (culled) {
+        if (mode != kModeUnit || a.s.sc.empty || a.s.sc.nsph) return hipErrorInvalidValue;
+        if (a.s.nt)
+            return a.s.sc.node6 ? launch_camera_cast_cull_t<Tracer6, true>(a, culled, s)
+                                : launch_camera_cast_cull_t<Tracer8, true>(a, culled, s);
+        return a.s.sc.node6 ? launch_camera_cast_cull_t<Tracer6, false>(a, culled, s)
+                            : launch_camera_cast_cull_t<Tracer8, false>(a, culled, s);
+    }
     if (a.s.nt)
         return a.s.sc.node6 ? launch_camera_cast_m<Tracer6, true>(a, mode, s)
                             : launch_camera_cast_m<Tracer8, true>(a, mode, s);

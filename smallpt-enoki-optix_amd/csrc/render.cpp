@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cassert>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -57,7 +58,11 @@ struct Stats {
     unsigned long long unwritten; // film slots still holding the sentinel at resolve time
     unsigned long long drained;   // paths finished by drain launches
     unsigned long long drained_casts;  // ray casts traced by drain launches
+    // bounce rays the camera casts ended at the BVH root (CameraCastArgs::culled):
+    // one counter per shard, each in a line of its own; render_collect sums them
+    alignas(128) unsigned long long culled[kShards][kCullStride];
 };
+constexpr size_t kStatsWords = 13;  // the 64-bit counters before `culled`
 
 // the drain phase starts when the host's (lagging) view of a stream's unstarted
 // work falls below this many queue capacities (spt_render_async)
@@ -543,9 +548,19 @@ spt_status render_collect(RenderSlot& r, Workspace& ws, spt_render_stats* out) {
     if (rs.tile_rows && !r.empty) {  // an empty tile (or pixel list) queued nothing
         HIP_TRY(hipEventSynchronize(r.done));
         const unsigned long long* hstats = reinterpret_cast<const unsigned long long*>(r.host);
-        static_assert(sizeof(Stats) == 13 * sizeof(unsigned long long), "Stats is the 13 counters read back here");
-        rs.ray_casts = hstats[0];
-        rs.continuations = hstats[1];
+        static_assert(offsetof(Stats, culled) >= kStatsWords * sizeof(unsigned long long) &&
+                          offsetof(Stats, drained_casts) == (kStatsWords - 1) * sizeof(unsigned long long),
+                      "Stats is the 13 counters read back here, then the culled shards");
+        // A culled bounce ray is a cast that was traced and ended in a miss, in
+        // the camera cast's launch: a cast and the continuation that led to it,
+        // as if the drain had traced it, but not drained.  (lockstep_casts stays
+        // the first casts: ray_casts - drained_casts == lockstep_casts + culled_paths
+        // where the camera cast ran.)
+        unsigned long long culled = 0;
+        for (uint32_t j = 0; j < kShards; j++) culled += r.host->culled[j][0];
+        rs.ray_casts = hstats[0] + culled;
+        rs.continuations = hstats[1] + culled;
+        rs.culled_paths = (uint32_t)std::min<unsigned long long>(culled, 0xffffffffull);
         rs.regenerations = hstats[2] > r.regen_base ? hstats[2] - r.regen_base : 0;
         rs.isect_nodes = hstats[3];
         rs.isect_tris = hstats[4];
@@ -1134,7 +1149,9 @@ spt_status run_iteration(RenderJob& j, SubRun& r, int k, uint64_t it) {
         ca.s.count_out = sharded ? &b.cnt->surv_shard[0][0] : &b.cnt->surv[nx];
         ca.s.shard_items = sharded ? r.known : 0u;
         ca.n = r.known;
-        if ((st = j.mark(1, sk, [&] { return launch_camera_cast(ca, mode, sk); }))) return st;
+        // the bounce cull (an empty scene has no root to visit, and no hit to bounce from)
+        unsigned long long* const culled = pl.bounce_cull && !ca.s.sc.empty ? &j.slot.dev->culled[0][0] : nullptr;
+        if ((st = j.mark(1, sk, [&] { return launch_camera_cast(ca, mode, sk, culled); }))) return st;
         if (sharded) {
             r.da.seg_count = &b.cnt->surv_shard[0][0];
             r.da.seg_items = r.known;

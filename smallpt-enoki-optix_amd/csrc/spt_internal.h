@@ -382,6 +382,12 @@ struct CameraCastArgs {
     ShadeArgs s;
     uint32_t n;
 };
+// launch_camera_cast's culled (unit mode, a non-empty scene without analytic
+// spheres; null: off): a bounce ray that misses every child of the BVH root
+// ends in the camera cast (camera_cast_cull_kernel); block b adds its count to
+// culled[(b % kShards) * kCullStride] (one 128-B line per shard: a single word
+// would take one atomic per block, shard_base.h).
+constexpr uint32_t kCullStride = 16;  // 64-bit words between the shards' culled counters
 
 // aov_kernel (spt_render_aov): the first-hit buffers of a tile of P pixels,
 // one lane per pixel over its spp samples.  Planes are P floats; NULL: skipped.
@@ -565,7 +571,7 @@ uint32_t isect_queue_lanes(const IsectQueueArgs& a);
 hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipStream_t s);
 // A fitting job's first cast — camera rays made, traced and shaded in one
 // launch (camera_cast_kernel); wide-BVH scenes.
-hipError_t launch_camera_cast(const CameraCastArgs& a, int mode, hipStream_t s);
+hipError_t launch_camera_cast(const CameraCastArgs& a, int mode, hipStream_t s, unsigned long long* culled = nullptr);
 hipError_t launch_refill(const RefillArgs& a, uint32_t grid_items, hipStream_t s);
 // The first-hit buffers of a tile (aov_kernel), every tree width.
 hipError_t launch_aov(const AovArgs& a, hipStream_t s);

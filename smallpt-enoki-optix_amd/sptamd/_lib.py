@@ -23,6 +23,7 @@ SPT_FLAG_TRAVERSAL_STATS = 2
 SPT_FLAG_FUSED = 4
 SPT_FLAG_WAVEFRONT = 8
 SPT_FLAG_TIMING_ALL = 16
+SPT_FLAG_NO_BOUNCE_CULL = 32
 PCG32_DEFAULT_STATE = 0x853C49E6748FEA9B
 SPT_BUILD_AUTO, SPT_BUILD_HOST_SAH, SPT_BUILD_GPU_PLOC = 0, 1, 2
 
@@ -104,7 +105,7 @@ class RenderStats(ctypes.Structure):
                 ("drained_paths", c_uint64), ("drain_launches", c_uint64), ("drained_casts", c_uint64),
                 ("drain_ms", c_double), ("drain_busy_ms", c_double), ("lockstep_casts", c_uint64),
                 ("fit_paths", c_uint64), ("fit_retries", c_uint64),
-                ("drain_refill_idle", c_uint32)]
+                ("drain_refill_idle", c_uint32), ("culled_paths", c_uint32)]
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
