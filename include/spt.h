@@ -434,6 +434,64 @@ spt_status spt_scene_set_material_kinds(spt_scene scene, const uint32_t* kinds, 
  * a scene that holds one (the cache does not store it; set it after loading). */
 spt_status spt_scene_set_envmap(spt_scene scene, const float* rgb, uint32_t n, const float* rotation);
 
+/* Light sampling — next-event estimation (a build addition).
+ * With the switch on, every diffuse path vertex that bounces (a surviving hit
+ * at cast j with j + 1 < max_depth, on a triangle or an analytic sphere) also
+ * samples one point on the scene's emissive triangles — light i with
+ * probability proportional to area_i x max(Le_i), the point uniformly on it —
+ * and traces one shadow ray to it — a closest-hit query that ends just behind
+ * the point; if the first thing it meets is the sampled triangle, as for a
+ * bounce ray in that direction, the path gathers throughput x Le x p cos' /
+ * (r^2 pdf), p the density with which the bounce sampler itself sends a ray
+ * that way (cos / pi for a unit shading normal).  The next hit of that path then
+ * adds no emission if it is a triangle with an emissive material (the light
+ * sample stood for it).  Camera rays and rays leaving a mirror or glass vertex
+ * count emission as always, and emissive spheres, the sky constant and the
+ * sky image are never sampled and always counted.  The expected image is the
+ * one of the switch off; its variance is lower
+ * wherever small emitters light the scene.  The numbers come from a side
+ * stream (a hash of global pixel, sample, cast), so a path's rays, hits,
+ * roulette and throughput are exactly those of the switch off, and ray_casts
+ * is unchanged; the shadow rays are counted apart (spt_scene_get_shadow_casts).
+ *
+ * The table is built here from the scene's own triangles and emission (f64 on
+ * the host: spt_light_table_build is the same code) and rebuilt by
+ * spt_scene_set_emission and spt_scene_update_geometry[_device] while the
+ * switch is on (a rebuild that fails turns it off and returns the error).  A
+ * scene with no emissive triangle, or whose weights sum to 0, has an empty
+ * table: the switch is then inert, every render bit-equal to the switch off.
+ * With a non-empty table every render of the scene runs the fused pipeline,
+ * whatever spt_config.pipeline and the job size say, and a render with
+ * SPT_FLAG_WAVEFRONT or SPT_FLAG_TRAVERSAL_STATS returns SPT_ERR_INVALID.
+ * spt_render_aov, spt_intersect and the denoisers do not read the switch.
+ * spt_scene_save refuses a scene with the switch on (the file does not store
+ * it; set it after loading).  Waits for queued renders like the other setters.
+ * SPT_ERR_INVALID: NULL scene, on > 1; SPT_ERR_LIMIT: more than 2^24 emissive
+ * triangles, or a traversal stack that no longer fits the device's LDS beside
+ * the light-sampling kernels' per-lane records; the scene is unchanged after
+ * an error.  spt_scene_get_light_sampling: the switch and the table's size. */
+spt_status spt_scene_set_light_sampling(spt_scene scene, uint32_t on);
+spt_status spt_scene_get_light_sampling(spt_scene scene, uint32_t* on, uint32_t* nlights);
+/* The shadow rays of the render collected last on this scene (spt_render,
+ * spt_render_accum[_list] and spt_render_wait collect one): closest-hit queries
+ * that are NOT part of ray_casts, continuations or any other count of
+ * spt_render_stats; 0 without the switch or with an empty table.  (A call of
+ * its own: spt_render_stats keeps the size earlier callers compiled against.) */
+spt_status spt_scene_get_shadow_casts(spt_scene scene, uint64_t* shadow_casts);
+
+/* Host only, no device: the light table of the given triangles (9 floats each,
+ * v0 v1 v2), materials (mat_id NULL: all 0) and emission (nmat x 3; NULL with
+ * nmat 0: none).  Members are the triangles whose material emits, in triangle
+ * order; area_i = |(v1 - v0) x (v2 - v0)| / 2 and w_i = area_i max(Le) in f64
+ * (a non-finite or non-positive w_i becomes 0: a member never chosen);
+ * cdf_i = f32(sum_{j <= i} w_j / sum w), the last forced to 1; pdf_area_i =
+ * f32(w_i / (sum w area_i)), 0 where w_i = 0.  sum w = 0: the table is empty.
+ * Two calls: with ids, cdf and pdf_area all NULL only *n_out is set; else the
+ * non-NULL ones take *n_out entries (capacity >= *n_out, or SPT_ERR_INVALID). */
+spt_status spt_light_table_build(const float* tri_vertices, const int32_t* mat_id, uint64_t ntri,
+                                 const float* emission_rgb, uint32_t nmat, uint32_t* ids, float* cdf,
+                                 float* pdf_area, uint32_t capacity, uint32_t* n_out);
+
 /* Host only, no device: resample a lat-long image (w x h interleaved RGB, rows
  * top-down; pbrt's convention theta = acos(z), phi = atan2(y, x), u = phi / 2pi
  * wrapped, v = theta / pi clamped, bilinear) to the n x n octahedral texel

@@ -22,6 +22,7 @@
 #include "gpu_build.h"
 #include "host_error.h"
 #include "render_plan.h"
+#include "light_table.h"
 #include "scene_state.h"
 #include "spt_internal.h"
 
@@ -72,10 +73,11 @@ uint32_t bvh8_stack_entries(uint32_t depth, uint32_t slack) {
 // The most LDS a workgroup of any trace kernel asks for with `stack_depth`
 // entries per lane (kernels.hip launch_*): the stack rows, for the wide
 // tracers the per-lane Woop and hit records behind them (Tracer8T::kExtraLds),
-// and the fused kernel's parked throughput / radiance (launch_fused_t).
-uint64_t stack_lds_bytes(uint32_t stack_depth, uint32_t width) {
+// and the fused kernel's parked throughput / radiance (launch_fused_t), with
+// light sampling also its parked bounce ray and contribution (nee).
+uint64_t stack_lds_bytes(uint32_t stack_depth, uint32_t width, bool nee) {
     return (uint64_t)stack_depth * kIsectBlock * sizeof(uint32_t) + (width != 2 ? 2u * kIsectBlock * 16u : 0u) +
-           kIsectBlock * 32u;
+           kIsectBlock * (nee ? 64u : 32u);
 }
 
 }  // namespace
@@ -115,15 +117,16 @@ spt_status ensure_device() {
 // before any kernel can be launched with it: the builders do not bound the
 // depth of a tree by what the device holds (the GPU builder does not bound it
 // at all), and a cache file may claim any stack_depth.
-spt_status check_stack_lds(const char* what, uint32_t stack_depth, uint32_t width) {
+spt_status check_stack_lds(const char* what, uint32_t stack_depth, uint32_t width, bool nee) {
     int dev = 0, cap = 0;
     (void)hipGetDevice(&dev);
     if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || cap <= 0)
         cap = 64 << 10;
-    const uint64_t need = stack_lds_bytes(stack_depth, width);
+    const uint64_t need = stack_lds_bytes(stack_depth, width, nee);
     if (need > (uint64_t)cap)
-        return fail(SPT_ERR_LIMIT, "%s: a traversal stack of depth %u (BVH width %u) needs %llu B of LDS per workgroup, "
-                    "the device has %d B", what, stack_depth, width, (unsigned long long)need, cap);
+        return fail(SPT_ERR_LIMIT, "%s: a traversal stack of depth %u (BVH width %u)%s needs %llu B of LDS per workgroup, "
+                    "the device has %d B", what, stack_depth, width, nee ? " with light sampling" : "",
+                    (unsigned long long)need, cap);
     return SPT_OK;
 }
 
@@ -549,10 +552,155 @@ spt_status spt_scene_set_albedo(spt_scene sc, const float* albedo_rgb, uint32_t 
     return SPT_OK;
 }
 
+namespace {
+
+// The scene's light table from its own records (light_table.h; caller holds
+// sc->mu, has made the device current and quiesced the scene).  *out: null for
+// an empty table; the scene is not touched.
+spt_status build_scene_lights(spt_scene_t* sc, const char* what, DeviceLights** out, uint32_t* nout) {
+    *out = nullptr;
+    *nout = 0;
+    if (!sc->emission || sc->nemit == 0 || sc->ntri == 0) return SPT_OK;
+    const uint32_t ntri = (uint32_t)sc->ntri;
+    std::vector<float> emi((size_t)sc->nemit * 3);
+    HIP_TRY(hipMemcpy(emi.data(), sc->emission, emi.size() * sizeof(float), hipMemcpyDeviceToHost));
+    struct Tmp {
+        int32_t* mat = nullptr;
+        uint32_t* ids = nullptr;
+        float* tv = nullptr;
+        ~Tmp() { hfree(mat); hfree(ids); hfree(tv); }
+    } d;
+    std::vector<int32_t> mat(ntri);
+    HIP_TRY(hipMalloc((void**)&d.mat, sizeof(int32_t) * ntri));
+    HIP_TRY(launch_light_mats(sc->snrm, sc->orig2slot, ntri, d.mat, nullptr));
+    HIP_TRY(hipMemcpy(mat.data(), d.mat, sizeof(int32_t) * ntri, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> ids;
+    std::vector<int32_t> lmat;
+    for (uint32_t t = 0; t < ntri; t++) {
+        const int32_t m = mat[t];
+        if (m < 0 || (uint32_t)m >= sc->nemit) continue;
+        if (emi[(size_t)m * 3] == 0.0f && emi[(size_t)m * 3 + 1] == 0.0f && emi[(size_t)m * 3 + 2] == 0.0f) continue;
+        ids.push_back(t);
+        lmat.push_back(m);
+    }
+    if (ids.empty()) return SPT_OK;
+    if (ids.size() > kMaxLights)
+        return fail(SPT_ERR_LIMIT, "%s: %zu emissive triangles (at most %u)", what, ids.size(), kMaxLights);
+    const uint32_t n = (uint32_t)ids.size();
+    std::vector<float> tv((size_t)n * 9);
+    spt_status us = upload(&d.ids, ids.data(), sizeof(uint32_t) * n);
+    if (us) return us;
+    HIP_TRY(hipMalloc((void**)&d.tv, sizeof(float) * 9 * n));
+    HIP_TRY(launch_light_tris(sc->tris, sc->orig2slot, d.ids, n, d.tv, nullptr));
+    HIP_TRY(hipMemcpy(tv.data(), d.tv, sizeof(float) * 9 * n, hipMemcpyDeviceToHost));
+    LightTable lt;
+    light_table_build(tv.data(), lmat.data(), n, emi.data(), sc->nemit, lt);
+    if (lt.empty()) return SPT_OK;
+    // (every compacted triangle is a member: the table's ids index `ids`)
+    std::vector<uint32_t> orig(lt.ids.size());
+    for (size_t i = 0; i < orig.size(); i++) orig[i] = ids[lt.ids[i]];
+    const size_t rec_bytes = lt.rec.size() * sizeof(float), cdf_bytes = lt.cdf.size() * sizeof(float);
+    std::vector<unsigned char> buf(sizeof(DeviceLights) + rec_bytes + cdf_bytes + orig.size() * sizeof(uint32_t));
+    DeviceLights h{};
+    h.n = (uint32_t)lt.ids.size();
+    std::memcpy(buf.data(), &h, sizeof(h));
+    std::memcpy(buf.data() + sizeof(h), lt.rec.data(), lt.rec.size() * sizeof(float));
+    std::memcpy(buf.data() + sizeof(h) + rec_bytes, lt.cdf.data(), cdf_bytes);
+    std::memcpy(buf.data() + sizeof(h) + rec_bytes + cdf_bytes, orig.data(), orig.size() * sizeof(uint32_t));
+    DeviceLights* dl = nullptr;
+    if ((us = upload(&dl, buf.data(), buf.size()))) return us;
+    *out = dl;
+    *nout = h.n;
+    return SPT_OK;
+}
+
+// After a change of the emission table or the geometry of a scene with the
+// switch on: the table again.  A table that cannot be rebuilt (or whose
+// kernels' LDS the device cannot hold) turns the switch off with the error.
+spt_status rebuild_scene_lights(spt_scene_t* sc, const char* what) {
+    if (!sc->light_sampling) return SPT_OK;
+    DeviceLights* dl = nullptr;
+    uint32_t n = 0;
+    spt_status st = build_scene_lights(sc, what, &dl, &n);
+    if (!st && dl && (st = check_stack_lds(what, sc->stack_depth, sc->cfg.bvh_width, true))) hfree(dl);
+    hfree(sc->lights);
+    sc->lights = st ? nullptr : dl;
+    sc->nlights = st ? 0 : n;
+    if (st) sc->light_sampling = false;
+    return st;
+}
+
+spt_status set_emission_locked(spt_scene_t* sc, const float* emission_rgb, uint32_t nmat);
+
+}  // namespace
+
+spt_status spt_scene_set_light_sampling(spt_scene sc, uint32_t on) {
+    static const char* what = "spt_scene_set_light_sampling";
+    if (!sc) return fail(SPT_ERR_INVALID, "%s: NULL scene", what);
+    if (on > 1) return fail(SPT_ERR_INVALID, "%s: on = %u (0 or 1)", what, on);
+    DeviceGuard dg(sc->device);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    spt_status st = quiesce_scene(sc);  // queued renders may still read the old table
+    if (st) return st;
+    DeviceLights* dl = nullptr;
+    uint32_t n = 0;
+    if (on) {
+        if ((st = build_scene_lights(sc, what, &dl, &n))) return st;
+        if (dl && (st = check_stack_lds(what, sc->stack_depth, sc->cfg.bvh_width, true))) {
+            hfree(dl);
+            return st;
+        }
+    }
+    hfree(sc->lights);
+    sc->lights = dl;
+    sc->nlights = n;
+    sc->light_sampling = on != 0;
+    return SPT_OK;
+}
+
+spt_status spt_scene_get_light_sampling(spt_scene sc, uint32_t* on, uint32_t* nlights) {
+    if (!sc) return fail(SPT_ERR_INVALID, "spt_scene_get_light_sampling: NULL scene");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (on) *on = sc->light_sampling ? 1u : 0u;
+    if (nlights) *nlights = sc->nlights;
+    return SPT_OK;
+}
+
+spt_status spt_light_table_build(const float* tri_vertices, const int32_t* mat_id, uint64_t ntri,
+                                 const float* emission_rgb, uint32_t nmat, uint32_t* ids, float* cdf, float* pdf_area,
+                                 uint32_t capacity, uint32_t* n_out) {
+    static const char* what = "spt_light_table_build";
+    if (!n_out) return fail(SPT_ERR_INVALID, "%s: NULL n_out", what);
+    if (ntri && !tri_vertices) return fail(SPT_ERR_INVALID, "%s: NULL vertices", what);
+    if (nmat && !emission_rgb) return fail(SPT_ERR_INVALID, "%s: NULL emission with nmat = %u", what, nmat);
+    if (ntri >= kMaxTriangles) return fail(SPT_ERR_LIMIT, "%s: %llu triangles exceeds 2^28", what, (unsigned long long)ntri);
+    LightTable lt;
+    light_table_build(tri_vertices, mat_id, ntri, emission_rgb, nmat, lt);
+    if (lt.ids.size() > kMaxLights)
+        return fail(SPT_ERR_LIMIT, "%s: %zu emissive triangles (at most %u)", what, lt.ids.size(), kMaxLights);
+    *n_out = (uint32_t)lt.ids.size();
+    if (!ids && !cdf && !pdf_area) return SPT_OK;  // the size call
+    if (capacity < lt.ids.size())
+        return fail(SPT_ERR_INVALID, "%s: capacity %u, the table has %zu lights", what, capacity, lt.ids.size());
+    for (size_t i = 0; i < lt.ids.size(); i++) {
+        if (ids) ids[i] = lt.ids[i];
+        if (cdf) cdf[i] = lt.cdf[i];
+        if (pdf_area) pdf_area[i] = lt.pdfA[i];
+    }
+    return SPT_OK;
+}
+
 spt_status spt_scene_set_emission(spt_scene sc, const float* emission_rgb, uint32_t nmat) {
     if (!sc) return fail(SPT_ERR_INVALID, "spt_scene_set_emission: NULL scene");
     DeviceGuard dg(sc->device);
     std::lock_guard<std::mutex> lk(sc->mu);
+    spt_status st = set_emission_locked(sc, emission_rgb, nmat);
+    if (st) return st;
+    return rebuild_scene_lights(sc, "spt_scene_set_emission");  // (the switch off: nothing)
+}
+
+namespace {
+spt_status set_emission_locked(spt_scene_t* sc, const float* emission_rgb, uint32_t nmat) {
     spt_status qs = quiesce_scene(sc);  // queued renders may still read the old table
     if (qs) return qs;
     hfree(sc->emission);
@@ -568,6 +716,7 @@ spt_status spt_scene_set_emission(spt_scene sc, const float* emission_rgb, uint3
     sc->nemit = nmat;
     return SPT_OK;
 }
+}  // namespace
 
 void spt_default_config(spt_config* c) {
     if (!c) return;
@@ -618,7 +767,8 @@ spt_status spt_scene_set_config(spt_scene sc, const spt_config* cfg) {
     // (stack_slack stays as built, below: the stack checked is the one the scene has)
     {
         DeviceGuard dg(sc->device);
-        if ((st = check_stack_lds("spt_scene_set_config", sc->stack_depth, sc->cfg.bvh_width))) return st;
+        if ((st = check_stack_lds("spt_scene_set_config", sc->stack_depth, sc->cfg.bvh_width, sc->lights != nullptr)))
+            return st;
     }
     const spt_config old = sc->cfg;
     sc->cfg = *cfg;
@@ -821,7 +971,7 @@ spt_status update_geometry_locked(spt_scene_t* sc, const RefitMeshIn& m, bool va
     st.area_built = p.area_built;
     st.area_now = area;
     st.update_ms = now_ms() - t0;
-    return SPT_OK;
+    return rebuild_scene_lights(sc, what);  // the lights moved with the rest (the switch off: nothing)
 }
 
 spt_status update_geometry_args(spt_scene sc, const int32_t* pos_tri, const float* pos, uint64_t ntri,

@@ -1496,12 +1496,27 @@ __global__ __launch_bounds__(kIsectBlock) void aov_kernel(AovArgs a) {
 // kEnv (albedo / emitter modes only): the scene has a sky image
 // (DeviceScene::envmap), looked up where a path escapes —
 // separate instances, so the others keep their registers and scratch.
-template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false>
+//
+// kNee (emitter mode, never with kDrain): the scene samples its emissive
+// triangles (DeviceScene::lights).  A lane that shades a
+// diffuse vertex works out the bounce ray as always, parks it with the
+// pending contribution in LDS (four float4 per lane instead of two) and
+// traces the shadow ray first, a closest-hit query that ends just behind the
+// light point; when that ray has finished the pass adds the contribution if
+// its hit is the sampled triangle — what a bounce ray in that direction would
+// have hit — and puts the bounce ray back, which goes through the same
+// tr.init below.  The
+// path's rays, hits, roulette and throughput are those of the other
+// instances.  park[1].z carries the path's "the next triangle hit drops its
+// emission" bit.
+template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
+          bool kNee = false>
 __global__ __launch_bounds__(kIsectBlock)
 __attribute__((amdgpu_waves_per_eu(kDrain && kMode == kModeUnit ? (kNt ? SPT_DRAIN_WAVES_NT : SPT_DRAIN_WAVES)
                                    : kDrain ? SPT_DRAIN_WAVES_RGB : SPT_FUSED_WAVES, 8)))
 void render_fused_kernel(FusedArgs a) {
     constexpr bool kEmit = kMode == kModeEmit;
+    static_assert(!kNee || (kEmit && !kDrain), "light sampling: emitter mode, not the drain");
 #if SPT_WAVE_LOG
     const unsigned long long wl_t0 = (unsigned long long)wall_clock64();
 #endif
@@ -1539,10 +1554,12 @@ void render_fused_kernel(FusedArgs a) {
     // so the traversal loop does not hold them in VGPRs
     constexpr bool kPark = kMode != kModeUnit;
     float4* const park = kPark ? (float4*)((char*)L.base + a.sc.stack_depth * kIsectBlock * 4u + Tr::kExtraLds) +
-                                     2u * threadIdx.x
+                                     (kNee ? 4u : 2u) * threadIdx.x
                                : nullptr;
     bool busy = false, pending = false;
+    bool shadow = false;  // kNee: the ray this lane traces is a shadow ray
     uint32_t casts = 0, conts = 0, starts = 0;  // wave-uniform
+    uint32_t shadows = 0;                       // kNee: shadow rays traced (wave-uniform)
     // wave-uniform work pool: static share, then dynamic chunks.  XCD-aware
     // (a.xcd_next): blocks are dealt round-robin over the 8 XCDs (block b on
     // XCD b mod 8, MI355X_MICROARCH.md), so the waves of one XCD take adjacent
@@ -1571,15 +1588,47 @@ void render_fused_kernel(FusedArgs a) {
             ph[5] += (uint32_t)__popcll(__ballot(pending));
 #endif
             // ---- shade every pending lane (shade_kernel, main.cpp:404-425)
-            casts += (uint32_t)__popcll(__ballot(pending));
+            if constexpr (kNee) {
+                casts += (uint32_t)__popcll(__ballot(pending && !shadow));
+                shadows += (uint32_t)__popcll(__ballot(pending && shadow));
+            } else {
+                casts += (uint32_t)__popcll(__ballot(pending));
+            }
             bool cont = false;
             bool need_init = false;  // a new ray in tr.o / dir to set up after the refill
+            if constexpr (kNee) {
+                if (pending && shadow) {
+                    // the shadow ray has finished: if the first thing it met is the
+                    // sampled triangle (a nearer analytic sphere occludes too), the
+                    // parked contribution joins the radiance; then the parked bounce
+                    // ray, from the same origin
+                    pending = false;
+                    shadow = false;
+                    TraceHit sh = tr.hit(a.sc, L);
+                    if (a.sc.nsph) {
+                        float tmn, tmx;
+                        light_shadow_interval(dir, tmn, tmx);
+                        trace_spheres(a.sc, tr.o, dir, tmn, false, sh);
+                    }
+                    const float4 p2 = park[2], p3 = park[3];
+                    if (sh.slot >= 0 && sh.id == f2u(p3.z)) {
+                        const float4 p0 = park[0], p1 = park[1];
+                        park[0] = make_float4(p0.x, p0.y, p0.z, p0.w + p2.w);
+                        park[1] = make_float4(p1.x + p3.x, p1.y + p3.y, p1.z, 0.0f);
+                    }
+                    dir = v3(p2.x, p2.y, p2.z);
+                    need_init = true;
+                    busy = true;
+                }
+            }
             if (pending) {
                 pending = false;
                 bool term = true;
+                uint32_t nee_prev = 0;  // kNee: the last vertex sampled the lights
                 if constexpr (kPark) {
                     const float4 p0 = park[0], p1 = park[1];
                     thr = p0.x; thg = p0.y; thb = p0.z; lr = p0.w; lg = p1.x; lb = p1.y;
+                    if constexpr (kNee) nee_prev = f2u(p1.z);
                 }
                 const uint32_t depth = meta & ((1u << kMetaDepthBits) - 1u), sample = meta >> kMetaDepthBits;
                 TraceHit hh = tr.hit(a.sc, L);
@@ -1601,7 +1650,8 @@ void render_fused_kernel(FusedArgs a) {
                 } else {
                     const float4 m0 = sph ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : a.sc.snrm[(size_t)slot * 3];
                     uint32_t mat = sph ? (a.sc.sph_mat ? (uint32_t)a.sc.sph_mat[-2 - slot] : 0u) : f2u(m0.w);
-                    if (kEmit && mat < a.sc.nemit) {
+                    // (kNee: an emissive triangle the last vertex could have sampled adds nothing)
+                    if (kEmit && mat < a.sc.nemit && !(kNee && nee_prev && !sph)) {
                         lr = lr + thr * a.sc.emission[mat * 3];
                         lg = lg + thg * a.sc.emission[mat * 3 + 1];
                         lb = lb + thb * a.sc.emission[mat * 3 + 2];
@@ -1647,13 +1697,41 @@ void render_fused_kernel(FusedArgs a) {
                                 dir = to_world(fr, cosine_hemisphere(xi_x, xi_y));  // main.cpp:418-419, 424
                             } else {  // Lambert on triangles as above; spheres / mirror / glass as smallpt
                                 float wgt;
-                                dir = scatter(a.sc, material_kind(a.sc, mat), slot, dir, hp, sn, xi_x, xi_y, wgt);
+                                const V3 din = dir;
+                                const uint32_t kind = material_kind(a.sc, mat);
+                                dir = scatter(a.sc, kind, slot, dir, hp, sn, xi_x, xi_y, wgt);
                                 thr = thr * wgt; thg = thg * wgt; thb = thb * wgt;
+                                if constexpr (kNee) {
+                                    nee_prev = 0;  // a mirror or glass vertex clears the bit
+                                    if (kind == kMatDiffuse) {
+                                        nee_prev = 1;
+                                        // the normal the bounce sampler made its frame from: the
+                                        // shading normal as interpolated (triangles), smallpt's nl
+                                        // (spheres; scatter)
+                                        V3 nh = sn;
+                                        if (sph) {
+                                            const float4 sp = a.sc.spheres[-2 - slot];
+                                            const V3 ns = normalize(v3(hp.x - sp.x, hp.y - sp.y, hp.z - sp.z));
+                                            nh = dot(ns, din) < 0.0f ? ns : v3(-ns.x, -ns.y, -ns.z);
+                                        }
+                                        V3 sd, sc3;
+                                        uint32_t lid;
+                                        if (light_sample(a.sc.lights, hp, nh, v3(thr, thg, thb),
+                                                         light_uniform(gpix, sample, depth, 0u),
+                                                         light_uniform(gpix, sample, depth, 1u),
+                                                         light_uniform(gpix, sample, depth, 2u), sd, sc3, lid)) {
+                                            park[2] = make_float4(dir.x, dir.y, dir.z, sc3.x);
+                                            park[3] = make_float4(sc3.y, sc3.z, u2f(lid), 0.0f);
+                                            dir = sd;
+                                            shadow = true;
+                                        }
+                                    }
+                                }
                             }
                             meta++;  // the next cast
                             if constexpr (kPark) {
                                 park[0] = make_float4(thr, thg, thb, lr);
-                                park[1] = make_float4(lg, lb, 0.0f, 0.0f);
+                                park[1] = make_float4(lg, lb, kNee ? u2f(nee_prev) : 0.0f, 0.0f);
                             }
                             tr.o = hp;  // traced from here: set up below with the refilled lanes
                             need_init = true;
@@ -1773,8 +1851,14 @@ void render_fused_kernel(FusedArgs a) {
                 // one ray set-up for the continued and the refilled lanes (one
                 // copy of the code instead of two); the last cast of a path is
                 // an any-hit query (unit mode)
-                tr.init(a.sc, tr.o, dir, kRayTmin, kRayTmax,
-                        (meta & ((1u << kMetaDepthBits) - 1u)) + 1u >= a.max_depth && !kEmit, L);
+                if constexpr (kNee) {  // a shadow ray: the closest hit over its own interval
+                    float tmn = kRayTmin, tmx = kRayTmax;
+                    if (shadow) light_shadow_interval(dir, tmn, tmx);
+                    tr.init(a.sc, tr.o, dir, tmn, tmx, false, L);
+                } else {
+                    tr.init(a.sc, tr.o, dir, kRayTmin, kRayTmax,
+                            (meta & ((1u << kMetaDepthBits) - 1u)) + 1u >= a.max_depth && !kEmit, L);
+                }
                 if (tr.finished()) {  // empty scene: a miss
                     busy = false;
                     pending = true;
@@ -1832,6 +1916,8 @@ void render_fused_kernel(FusedArgs a) {
         if (casts) atomicAdd(&a.stats[0], (unsigned long long)casts);
         if (conts) atomicAdd(&a.stats[1], (unsigned long long)conts);
         if (starts) atomicAdd(&a.stats[2], (unsigned long long)starts);
+        if constexpr (kNee)
+            if (shadows) atomicAdd(&a.stats[kStatShadowWord], (unsigned long long)shadows);
     }
 }
 
@@ -2371,19 +2457,21 @@ hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipSt
     return hipGetLastError();
 }
 
-template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false>
+template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
+          bool kNee = false>
 static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
     static thread_local size_t cached_lds = 0;
     static thread_local uint32_t cached = 0;
     static thread_local int cached_dev = -1;
     // + the parked throughput / radiance of albedo / emitter lanes (render_fused_kernel)
-    const size_t park = kMode != kModeUnit ? (size_t)kIsectBlock * 32 : 0;
+    // (kNee: + the parked bounce ray and pending contribution; check_stack_lds counts the same)
+    const size_t park = kMode != kModeUnit ? (size_t)kIsectBlock * (kNee ? 64 : 32) : 0;
     const size_t lds = (size_t)a.sc.stack_depth * Tr::kStackWords * kIsectBlock * sizeof(uint32_t) + Tr::kExtraLds + park;
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (!cached || cached_lds != lds || cached_dev != dev) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv>,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee>,
                                                          kIsectBlock, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -2396,13 +2484,20 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     // (the drain's grid cannot follow its count, which is on the device)
     const uint32_t blocks = kDrain ? scaled : min(scaled, blocks_for(a.count > 0 ? a.count : 1, kIsectBlock));
     if (lanes_out) *lanes_out = blocks * kIsectBlock;
-    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv>), dim3(blocks), dim3(kIsectBlock), lds, s, a);
+    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee>), dim3(blocks), dim3(kIsectBlock),
+                       lds, s, a);
     return hipGetLastError();
 }
 
 // a scene with a sky image takes the kEnv instance (never in unit mode, spt_render)
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false>
 static hipError_t launch_fused_e(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
+    // a scene with a light table takes the kNee instance (emitter mode, never the drain: the plan)
+    if constexpr (kMode == kModeEmit && !kDrain && !kNt)
+        if (a.sc.lights) {
+            if (a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true>(a, s, lanes_out);
+            return launch_fused_t<Tr, kMode, kDrain, kNt, kList, false, true>(a, s, lanes_out);
+        }
     if constexpr (kMode != kModeUnit)
         if (a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true>(a, s, lanes_out);
     return launch_fused_t<Tr, kMode, kDrain, kNt, kList>(a, s, lanes_out);

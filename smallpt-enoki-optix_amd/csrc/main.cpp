@@ -22,7 +22,7 @@
 //                  [--gpus N] [--rows-per-group R] [--rehearse-shared-gpu]
 //                  [--aov PREFIX] [--denoise [--denoise-iters N]]
 //                  [--passes N] [--variance FILE] [--denoise-var]
-//                  [--envmap sky.pfm [--env-res N] | --envmap-oct sky.pfm] [--env-rotate-y DEG]
+//                  [--envmap sky.pfm [--env-res N] | --envmap-oct sky.pfm] [--env-rotate-y DEG] [--nee]
 //
 // --aov PREFIX writes the first-hit buffers of the render (spt_render_aov) as
 // PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm (depth in all three
@@ -47,6 +47,12 @@
 // written its file (the cache does not store it), so the flags work with a
 // .sptc scene too, and with --passes, --adaptive, --aov and --denoise*.
 // Single-device.
+//
+// --nee switches light sampling on (spt_scene_set_light_sampling: a shadow ray
+// to the emissive triangles at every diffuse vertex), after --save-cache for
+// the same reason.  It works with every other flag, --gpus included: each
+// rank builds the same table from the same triangles, and the side stream is
+// keyed by the global pixel.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -95,7 +101,8 @@ struct Rank {
 // Renders p over ranks.size() tiles and assembles the (3, H, W) image on the
 // host.  The scene is committed on each device (or loaded from the cache).
 void render_multi(const std::string& path, const spt::Mesh* mesh, spt_render_params p, int ngpu, bool shared,
-                  uint32_t rows_per_group, std::vector<float>& image, spt_render_stats& total, double& ms) {
+                  uint32_t rows_per_group, std::vector<float>& image, spt_render_stats& total, double& ms,
+                  bool nee = false) {
     int ndev = 0;
     hip_check(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
     if (!shared && ngpu > ndev)
@@ -133,6 +140,7 @@ void render_multi(const std::string& path, const spt::Mesh* mesh, spt_render_par
     each([&](Rank& k) {
         if (mesh) k.scene.commit_from(*mesh, k.device);
         else k.scene.load(path, k.device);
+        if (nee) k.scene.set_light_sampling();  // every rank's own table: the same triangles, the same table
         hip_check(hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking), "hipStreamCreate");
         hip_check(hipEventCreateWithFlags(&k.done, hipEventDisableTiming), "hipEventCreate");
         hip_check(hipMalloc((void**)&k.tile, sizeof(float) * count), "hipMalloc tile");
@@ -238,6 +246,7 @@ int main(int argc, char** argv) {
     bool envmap_oct = false, env_rotate = false;
     int env_res = 512;
     double env_rotate_y = 0.0;  // degrees
+    bool nee = false;           // --nee: spt_scene_set_light_sampling
     int denoise_iters = -1;  // -1: spt_default_denoise_params
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
@@ -278,6 +287,7 @@ int main(int argc, char** argv) {
         else if (a == "--envmap-oct") { envmap_in = next(); envmap_oct = true; }
         else if (a == "--env-res") env_res = std::atoi(next());
         else if (a == "--env-rotate-y") { env_rotate_y = std::atof(next()); env_rotate = true; }
+        else if (a == "--nee") nee = true;
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
     }
@@ -365,6 +375,7 @@ int main(int argc, char** argv) {
                 scene.set_envmap(oct.data(), (uint32_t)env_res, env_rotate ? rot : nullptr);
             }
         }
+        if (nee && ngpu < 1) scene.set_light_sampling();  // after the save: the cache does not store the switch
         if (pi.has_camera) {
             p.camera = pi.camera;
             if (!set_w) p.width = pi.xres;
@@ -377,7 +388,7 @@ int main(int argc, char** argv) {
         spt_render_stats st{};
         double ms = 0.0;
         if (ngpu >= 1) {
-            render_multi(obj, mesh.get(), p, ngpu, shared, rows_per_group, host, st, ms);
+            render_multi(obj, mesh.get(), p, ngpu, shared, rows_per_group, host, st, ms, nee);
             std::cout << ms << std::endl;  // main.cpp:431 (render + gather)
         } else {
             float* film = nullptr;

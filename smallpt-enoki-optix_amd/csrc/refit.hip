@@ -325,4 +325,42 @@ hipError_t refit_plan_build(const RefitScene& sc, uint64_t expected_nodes, hipSt
     return hipSuccess;
 }
 
+// ---- the light table's inputs (spt_scene_set_light_sampling, capi.cpp): the
+// host keeps no copy of the triangles, so the material id of every triangle
+// and the vertices of the emissive ones are read back from the records, in
+// original triangle id order (orig2slot).
+
+__global__ __launch_bounds__(256) void light_mats_kernel(const float4* __restrict__ snrm,
+                                                         const int32_t* __restrict__ orig2slot, uint32_t ntri,
+                                                         int32_t* __restrict__ mat) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= ntri) return;
+    mat[t] = (int32_t)f2u(snrm[(size_t)orig2slot[t] * 3].w);
+}
+
+__global__ __launch_bounds__(256) void light_tris_kernel(const float4* __restrict__ tris,
+                                                         const int32_t* __restrict__ orig2slot,
+                                                         const uint32_t* __restrict__ ids, uint32_t n,
+                                                         float* __restrict__ tv) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float* rec = (const float*)(tris + (size_t)orig2slot[ids[i]] * kTriQuads);  // tri_record_fill
+    for (uint32_t k = 0; k < 3; k++)
+        for (uint32_t c = 0; c < 3; c++) tv[(size_t)i * 9 + 3 * k + c] = rec[5 * k + c];
+}
+
+hipError_t launch_light_mats(const float4* snrm, const int32_t* orig2slot, uint32_t ntri, int32_t* mat,
+                             hipStream_t s) {
+    if (!ntri) return hipSuccess;
+    hipLaunchKernelGGL(light_mats_kernel, dim3((ntri + 255u) / 256u), dim3(256), 0, s, snrm, orig2slot, ntri, mat);
+    return hipGetLastError();
+}
+
+hipError_t launch_light_tris(const float4* tris, const int32_t* orig2slot, const uint32_t* ids, uint32_t n,
+                             float* tv, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(light_tris_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, tris, orig2slot, ids, n, tv);
+    return hipGetLastError();
+}
+
 }  // namespace spt

@@ -61,8 +61,11 @@ struct Stats {
     // bounce rays the camera casts ended at the BVH root (CameraCastArgs::culled):
     // one counter per shard, each in a line of its own; render_collect sums them
     alignas(128) unsigned long long culled[kShards][kCullStride];
+    unsigned long long shadow;    // shadow rays the light-sampling fused kernels traced (kStatShadowWord)
 };
 constexpr size_t kStatsWords = 13;  // the 64-bit counters before `culled`
+static_assert(offsetof(Stats, shadow) == kStatShadowWord * sizeof(unsigned long long),
+              "the fused kernel finds the shadow counter from Stats::stats");
 
 // the drain phase starts when the host's (lagging) view of a stream's unstarted
 // work falls below this many queue capacities (spt_render_async)
@@ -235,6 +238,8 @@ struct spt::Workspace {
     // across overlapping queued renders is exact (not one render's span less
     // its overlap)
     bool collect_iv = false;
+    // shadow rays of the render collected last (spt_scene_get_shadow_casts)
+    uint64_t last_shadow_casts = 0;
     std::vector<std::pair<double, double>> iv_all[2];
 
     void release() {
@@ -575,6 +580,7 @@ spt_status render_collect(RenderSlot& r, Workspace& ws, spt_render_stats* out) {
         rs.isect_node_wave_steps = hstats[9];
         rs.drained_paths = hstats[11];
         rs.drained_casts = hstats[12];
+        ws.last_shadow_casts = r.host->shadow;
         if (r.timing) {
             uint64_t nis = 0;
             // launch intervals from the origin: [0] isect (the fused kernel in
@@ -748,6 +754,7 @@ RenderPlanIn plan_inputs(const spt_scene_t* sc, const spt_render_params& p, uint
     in.device_bytes = sc->stats.device_bytes;
     in.nsph = sc->nsph;
     in.wide_nodes = sc->nodes8 != nullptr;
+    in.nee = sc->lights != nullptr;
     in.null_caller = caller == nullptr || caller == hipStreamLegacy || caller == hipStreamPerThread;
     if (const WorkSet* hs = sc->ws.bound_set(caller)) {
         for (int k = 0; k < kMaxStreams; k++) {
@@ -1353,6 +1360,11 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
     const uint32_t sample_base = accum ? accum->sample_base : 0u;
     DeviceGuard dg(sc->device);
     std::lock_guard<std::mutex> lock(sc->mu);  // the scene's one workspace
+    // light sampling lives in the fused lane loop only: refused
+    // before any device work rather than rendered with another estimator
+    if (sc->lights && (p.flags & (SPT_FLAG_WAVEFRONT | SPT_FLAG_TRAVERSAL_STATS)))
+        return fail(SPT_ERR_INVALID, "spt_render: SPT_FLAG_WAVEFRONT / SPT_FLAG_TRAVERSAL_STATS on a scene with light "
+                    "sampling on (it runs in the fused pipeline only; spt_scene_set_light_sampling(scene, 0) first)");
     RenderSlot* slot = nullptr;
     if ((st = render_slot(sc->ws, &slot))) return st;
     spt_render_stats& rs = slot->rs;
@@ -1494,6 +1506,13 @@ spt_status spt_render_wait(spt_scene sc, uint64_t ticket, spt_render_stats* stat
         return fail(SPT_ERR_INVALID, "spt_render_wait: ticket %llu is not a queued render (already collected, "
                     "or %d renders were queued after it)", (unsigned long long)ticket, kRenderSlots);
     return render_collect(r, sc->ws, stats_out);
+}
+
+spt_status spt_scene_get_shadow_casts(spt_scene sc, uint64_t* out) {
+    if (!sc || !out) return fail(SPT_ERR_INVALID, "spt_scene_get_shadow_casts: NULL argument");
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *out = sc->ws.last_shadow_casts;
+    return SPT_OK;
 }
 
 spt_status spt_render(spt_scene sc, const spt_render_params* pp, float* film_dev, spt_render_stats* stats_out,

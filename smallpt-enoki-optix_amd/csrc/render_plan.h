@@ -74,6 +74,11 @@ struct RenderPlanIn {
     uint64_t device_bytes = 0;
     uint32_t nsph = 0;
     bool wide_nodes = false;
+    // the scene samples its emissive triangles (spt_scene_set_light_sampling with
+    // a non-empty table): only the fused lane loop has that estimator, so the
+    // plan is the fused pipeline whatever spt_config.pipeline, the flags and the
+    // job size say (the render refuses SPT_FLAG_WAVEFRONT / _TRAVERSAL_STATS first)
+    bool nee = false;
     // the caller renders on a null stream (legacy or per-thread)
     bool null_caller = false;
     // what the working set bound to the caller's stream holds already (zeros:
@@ -159,6 +164,7 @@ inline RenderPlan plan_render(const RenderPlanIn& in, uint64_t fit_limit) {
     fused = cfg.pipeline == SPT_PIPELINE_AUTO ? jobs <= fused_max : cfg.pipeline == SPT_PIPELINE_FUSED;
     if (in.flags & SPT_FLAG_FUSED) fused = true;
     if ((in.flags & SPT_FLAG_WAVEFRONT) || trav_stats) fused = false;
+    if (in.nee) fused = true;  // light sampling: the fused kernel's kNee instances
     // Work order (spt_config.work_order).  AUTO, measured (DESIGN.md §4,
     // profiles/r02_workorder): pixel-major for a scene larger than the
     // Infinity Cache (config 4: +3.8 %; the paths in flight then cover a band

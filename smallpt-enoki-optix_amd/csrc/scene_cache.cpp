@@ -300,6 +300,9 @@ spt_status spt_scene_save(spt_scene sc, const char* path, const void* extra, uin
     if (sc->envmap)  // the format has no section for it yet: refuse rather than drop the sky silently
         return fail(SPT_ERR_INVALID, "%s: the scene holds an environment map, which the cache does not store "
                     "(remove it with spt_scene_set_envmap(scene, NULL, 0, NULL), save, and set it again after loading)", what);
+    if (sc->light_sampling)  // likewise: the file would come back with another estimator
+        return fail(SPT_ERR_INVALID, "%s: the scene has light sampling on, which the cache does not store "
+                    "(spt_scene_set_light_sampling(scene, 0), save, and switch it on again after loading)", what);
     CacheHeader h;
     std::memset(&h, 0, sizeof(h));
     std::memcpy(h.magic, kCacheMagic, 8);

@@ -91,6 +91,11 @@ struct spt_scene_t {
     // the sky image (spt_scene_set_envmap): the device struct and the texels behind it
     spt::DeviceEnvMap* envmap = nullptr;
     float4* env_texels = nullptr;
+    // light sampling (spt_scene_set_light_sampling): the switch, and the table
+    // built from the scene's emissive triangles (null: off, or an empty table)
+    bool light_sampling = false;
+    spt::DeviceLights* lights = nullptr;
+    uint32_t nlights = 0;
     uint64_t node_bytes = 0;  // bytes behind nodes / nodes8 (spt_scene_save)
     uint32_t stack_depth = 1;
     spt_scene_stats stats{};
@@ -111,6 +116,7 @@ struct spt_scene_t {
         d.spheres = spheres; d.sph_mat = sph_mat; d.nsph = nsph;
         d.mat_kind = mat_kind; d.nkind = nkind;
         d.envmap = envmap;
+        d.lights = lights;
         return d;
     }
     void release() {
@@ -120,6 +126,7 @@ struct spt_scene_t {
         spt::hfree(nodes); spt::hfree(nodes8); spt::hfree(emission); spt::hfree(tris); spt::hfree(snrm); spt::hfree(tc); spt::hfree(orig2slot); spt::hfree(albedo);
         spt::hfree(tex_info); spt::hfree(texels); spt::hfree(spheres); spt::hfree(sph_mat); spt::hfree(mat_kind);
         spt::hfree(envmap); spt::hfree(env_texels);
+        spt::hfree(lights);
         spt::refit_plan_release(refit);
         spt::hfree(refit_bad);
     }
@@ -154,7 +161,8 @@ spt_status upload_textures(spt_scene_t* sc);
 // Range checks of spt_scene_set_config / spt_scene_create_cfg.
 spt_status check_config(const spt_config& c);
 // Refuses a stack that does not fit the current device's LDS per workgroup.
-spt_status check_stack_lds(const char* what, uint32_t stack_depth, uint32_t width);
+// nee: with the light-sampling kernels' larger park (launch_fused_t).
+spt_status check_stack_lds(const char* what, uint32_t stack_depth, uint32_t width, bool nee = false);
 
 template <typename T>
 spt_status upload(T** dst, const void* src, size_t bytes) {

@@ -121,6 +121,10 @@ class Scene {
     void set_envmap(const float* rgb, uint32_t n, const float* rotation = nullptr) {
         check(spt_scene_set_envmap(scene_, rgb, n, rotation), "spt_scene_set_envmap");
     }
+    // spt_scene_set_light_sampling: next-event estimation on the emissive triangles
+    void set_light_sampling(bool on = true) {
+        check(spt_scene_set_light_sampling(scene_, on ? 1u : 0u), "spt_scene_set_light_sampling");
+    }
     spt_refit_stats refit_stats() const {
         spt_refit_stats st{};
         check(spt_scene_get_refit_stats(scene_, &st), "spt_scene_get_refit_stats");

@@ -76,6 +76,7 @@ struct PathQueue {
 };
 
 struct DeviceEnvMap;
+struct DeviceLights;
 
 // Geometry on device, leaf ("slot") order.
 struct DeviceScene {
@@ -102,6 +103,7 @@ struct DeviceScene {
     const uint32_t* mat_kind;  // per material SPT_MAT_* (null: every material diffuse)
     uint32_t nkind;
     const DeviceEnvMap* envmap;  // the sky image (spt_scene_set_envmap; null: the constant params.env)
+    const DeviceLights* lights;  // the light table (spt_scene_set_light_sampling; null: off, or an empty table)
 };
 
 // The environment map on the device: an octahedral image of
@@ -158,6 +160,75 @@ SPT_HD V3 env_radiance(const DeviceScene& sc, V3 d) {
     const V3 top = v3(ux * t00.x + wx * t10.x, ux * t00.y + wx * t10.y, ux * t00.z + wx * t10.z);
     const V3 bot = v3(ux * t01.x + wx * t11.x, ux * t01.y + wx * t11.y, ux * t01.z + wx * t11.z);
     return v3(uy * top.x + wy * bot.x, uy * top.y + wy * bot.y, uy * top.z + wy * bot.z);
+}
+
+// The light table on the device (light_table.h): one allocation
+// behind one pointer in DeviceScene — this header, then n records of four
+// quads (light_table.h), then the n floats of the cdf, then the n original
+// triangle ids.
+struct DeviceLights {
+    uint32_t n;
+    uint32_t pad[3];
+};
+SPT_HD const float4* light_recs(const DeviceLights* l) { return (const float4*)(l + 1); }
+SPT_HD const float* light_cdf(const DeviceLights* l) { return (const float*)(light_recs(l) + (size_t)l->n * 4u); }
+SPT_HD const uint32_t* light_ids(const DeviceLights* l) { return (const uint32_t*)(light_cdf(l) + l->n); }
+
+// Light sampling at a diffuse path vertex x: the light i with
+// the smallest cdf_i > xi0, the point y on it by light_tri_map(xi1, xi2), the
+// shadow ray x -> y as d = y - x (un-normalised, its closest hit sought over
+// [kRayTmin rl, 1 + kRayTmin rl], rl = 1 / |d|: light_shadow_interval) and the
+// contribution c = (T Le) g the path gathers if that hit is the light itself,
+// original triangle `id`.  nf: the normal the bounce sampler builds its frame
+// from at x, as it takes it (a triangle's interpolated shading normal, not
+// normalised; smallpt's nl on a sphere).  The bounce direction is M l with
+// M = frame_from_normal(nf) and l cosine-distributed about +y, so the density
+// of its direction d rl is cx / pi with
+//   v = (d . by x bz, d . bz x bx, d . bx x by)       (= det M  M^-1 d)
+//   cx = ((v.y det) |det|) / ((v.v)^2 ((rl rl) rl))    (= (nf . d) rl for an orthonormal M)
+// and the light is weighed with that density, so the expectation is the bounce
+// sampler's own whatever the length of nf.  False: no shadow ray (a point nearer than the rays' own offset, a light
+// facing away or seen edge-on, a g that is not finite, or c = 0 in every
+// channel).  f32, every operation rounded, in this order: tests/nee_ref.py
+// restates it.
+SPT_HD void light_shadow_interval(V3 d, float& tmin, float& tmax) {
+    const float rl = 1.0f / sqrtf(dot(d, d));
+    tmin = kRayTmin * rl;
+    tmax = 1.0f + tmin;
+}
+SPT_HD bool light_sample(const DeviceLights* lt, V3 x, V3 nf, V3 T, float xi0, float xi1, float xi2, V3& d, V3& c,
+                         uint32_t& id) {
+    const float* cdf = light_cdf(lt);
+    uint32_t lo = 0, hi = lt->n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (xi0 < cdf[mid]) hi = mid;
+        else lo = mid + 1u;
+    }
+    id = light_ids(lt)[lo];
+    const float4* r = light_recs(lt) + (size_t)lo * 4u;
+    const float4 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3];
+    float b1, b2;
+    light_tri_map(xi1, xi2, b1, b2);
+    const float b0 = (1.0f - b1) - b2;
+    const V3 y = v3((b0 * q0.x + b1 * q0.w) + b2 * q1.z, (b0 * q0.y + b1 * q1.x) + b2 * q1.w,
+                    (b0 * q0.z + b1 * q1.y) + b2 * q2.x);
+    d = v3(y.x - x.x, y.y - x.y, y.z - x.z);
+    c = v3(0.0f, 0.0f, 0.0f);
+    const float rl = 1.0f / sqrtf(dot(d, d));
+    const float tmin = kRayTmin * rl;
+    if (!(tmin <= 1.0f)) return false;
+    const Frame fr = frame_from_normal(nf);
+    const V3 c1 = cross(fr.by, fr.bz), c2 = cross(fr.bz, fr.bx), c3 = cross(fr.bx, fr.by);
+    const float det = dot(fr.bx, c1);
+    const V3 v = v3(dot(d, c1), dot(d, c2), dot(d, c3));
+    const float vv = dot(v, v);
+    const float cx = ((v.y * det) * fabsf(det)) / ((vv * vv) * ((rl * rl) * rl));
+    const float cy = fabsf(dot(v3(q2.y, q2.z, q2.w), d)) * rl;
+    const float g = (((cx * cy) * rl) * rl) / (kPi * q3.w);
+    if (!(cx > 0.0f) || !(cy > 0.0f) || !(g < INFINITY)) return false;
+    c = v3((T.x * q3.x) * g, (T.y * q3.y) * g, (T.z * q3.z) * g);
+    return c.x != 0.0f || c.y != 0.0f || c.z != 0.0f;
 }
 
 constexpr uint32_t kMatDiffuse = 0, kMatMirror = 1, kMatGlass = 2;  // SPT_MAT_*
@@ -436,7 +507,8 @@ struct FusedArgs {
     const PcgJump* sample_jump;
     float* sfilm;               // [spp_chunk][3][P] (albedo / emit)
     uint8_t* sflag;             // [spp_chunk][P] (unit mode)
-    unsigned long long* stats;  // casts, continuations, regenerations
+    unsigned long long* stats;  // casts, continuations, regenerations; the kNee instances add their
+                                // shadow casts to stats[kStatShadowWord] (render.cpp Stats::shadow)
     uint32_t* next;             // dynamic work counter (zeroed before the launch)
     uint64_t work0, initstate;
     uint32_t count, P, W, sample0, max_depth, rr_start, rng_order;
@@ -472,6 +544,10 @@ struct FusedArgs {
     const uint32_t* list;
     uint32_t list_n;
 };
+
+// 64-bit words from FusedArgs::stats (the head of render.cpp's Stats) to its
+// shadow-cast counter, which sits behind the culled shards
+constexpr uint32_t kStatShadowWord = 16 + kShards * kCullStride;
 
 struct HitInfoArgs {
     DeviceScene sc;
@@ -688,5 +764,13 @@ hipError_t launch_refit_validate(const RefitScene& sc, const RefitMeshIn& m, uin
 // records give).  *plan.area holds the sum of half areas afterwards.
 hipError_t launch_refit_update(const RefitScene& sc, const RefitMeshIn* m, const RefitPlan& plan, bool write,
                                hipStream_t s);
+
+// ---- the light table's inputs (refit.hip, spt_scene_set_light_sampling)
+// mat[t] = the material id of original triangle t (ntri entries)
+hipError_t launch_light_mats(const float4* snrm, const int32_t* orig2slot, uint32_t ntri, int32_t* mat,
+                             hipStream_t s);
+// tv[9 i ..] = the three vertices of original triangle ids[i], i < n, from its record
+hipError_t launch_light_tris(const float4* tris, const int32_t* orig2slot, const uint32_t* ids, uint32_t n,
+                             float* tv, hipStream_t s);
 
 }  // namespace spt

@@ -422,4 +422,27 @@ SPT_HD float rr_uniform(uint32_t pixel, uint32_t sample, uint32_t depth) {
     return (float)(h >> 8) * (1.0f / 16777216.0f);
 }
 
+// ------------------------------------------------------------ light sampling
+// The light-sampling side stream: number k = 0, 1, 2 of the
+// vertex a path (pixel, sample) reaches at cast `depth`.  As rr_uniform, a
+// counter-based hash with constants of its own, so neither the PCG32 draw
+// layout nor the roulette's numbers move.
+SPT_HD float light_uniform(uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t k) {
+    uint32_t h = pixel * 0x8DA6B343u ^ (sample + 0x2545F491u) * 0xD8163841u ^ (depth * 3u + k + 1u) * 0xCB1AB31Fu;
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+    return (float)(h >> 8) * (1.0f / 16777216.0f);
+}
+
+// Heitz's low-distortion map of the unit square to barycentrics (no sqrt):
+// the point is (1 - b1 - b2) v0 + b1 v1 + b2 v2.
+SPT_HD void light_tri_map(float xi1, float xi2, float& b1, float& b2) {
+    if (xi2 > xi1) {
+        b1 = xi1 / 2.0f;
+        b2 = xi2 - b1;
+    } else {
+        b2 = xi2 / 2.0f;
+        b1 = xi1 - b2;
+    }
+}
+
 }  // namespace spt

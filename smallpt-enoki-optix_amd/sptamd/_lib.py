@@ -44,6 +44,8 @@ EXPORTED = [
     "spt_default_denoise_var_params", "spt_denoise_var_scratch_bytes", "spt_denoise_var",
     "spt_default_adapt_params", "spt_adapt_select_scratch_bytes", "spt_adapt_select", "spt_render_accum_list",
     "spt_scene_set_envmap", "spt_envmap_from_latlong", "spt_pfm_read", "spt_pfm_free",
+    "spt_scene_set_light_sampling", "spt_scene_get_light_sampling", "spt_light_table_build",
+    "spt_scene_get_shadow_casts",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -270,6 +272,10 @@ def _load() -> ctypes.CDLL:
                                         POINTER(RenderStats), vp]),
         "spt_scene_set_envmap": (i32, [vp, vp, u32, vp]),
         "spt_envmap_from_latlong": (i32, [vp, u32, u32, u32, vp]),
+        "spt_scene_set_light_sampling": (i32, [vp, u32]),
+        "spt_scene_get_light_sampling": (i32, [vp, vp, vp]),
+        "spt_scene_get_shadow_casts": (i32, [vp, vp]),
+        "spt_light_table_build": (i32, [vp, vp, u64, vp, u32, vp, vp, vp, u32, vp]),
         "spt_pfm_read": (i32, [c_char_p, POINTER(POINTER(ctypes.c_float)), POINTER(u32), POINTER(u32)]),
         "spt_pfm_free": (None, [POINTER(ctypes.c_float)]),
     }

@@ -230,6 +230,31 @@ class HipBackend:
         check(lib.spt_scene_set_envmap(self._scene, img.ctypes.data, img.shape[0], _host_ptr(rot)),
               "spt_scene_set_envmap")
 
+    def set_light_sampling(self, on=True) -> None:
+        """spt_scene_set_light_sampling: sample the scene's emissive triangles with a
+        shadow ray at every diffuse path vertex (next-event estimation).  Renders of
+        such a scene run the fused pipeline; stats["shadow_casts"] counts the rays."""
+        check(lib.spt_scene_set_light_sampling(self._scene, 1 if on else 0), "spt_scene_set_light_sampling")
+
+    def shadow_casts(self) -> int:
+        """spt_scene_get_shadow_casts: the shadow rays of the render collected last."""
+        n = ctypes.c_uint64(0)
+        check(lib.spt_scene_get_shadow_casts(self._scene, ctypes.byref(n)), "spt_scene_get_shadow_casts")
+        return int(n.value)
+
+    def _stats(self, st) -> dict:
+        """A collected render's stats dict, with its shadow_casts."""
+        d = st.as_dict()
+        d["shadow_casts"] = self.shadow_casts()
+        return d
+
+    def light_sampling(self):
+        """(on, lights): the switch and the size of the scene's light table."""
+        on, n = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib.spt_scene_get_light_sampling(self._scene, ctypes.byref(on), ctypes.byref(n)),
+              "spt_scene_get_light_sampling")
+        return bool(on.value), int(n.value)
+
     def set_texture(self, material: int, image=None) -> None:
         """Material `material`'s reflectance image (ImageTexture, main.cpp:34-80):
         (H, W, 3) float32, or None to remove it."""
@@ -531,7 +556,7 @@ class Scene:
         self.backend.sync_config()
         check(lib.spt_render(self.backend.handle, ctypes.byref(params), film.data_ptr(), ctypes.byref(st),
                              _stream_handle(stream)), "spt_render")
-        return film, st.as_dict()
+        return film, self.backend._stats(st)
 
     def render_async(self, params: RenderParams, film: Optional[torch.Tensor] = None, stream=None):
         """spt_render_async: queue the render and return (film, ticket) without
@@ -547,7 +572,7 @@ class Scene:
         """spt_render_wait: the stats dict of a queued render (waits for it)."""
         st = RenderStats()
         check(lib.spt_render_wait(self.backend.handle, ticket, ctypes.byref(st)), "spt_render_wait")
-        return st.as_dict()
+        return self.backend._stats(st)
 
     def accumulator(self, params: RenderParams, moments: bool = True) -> "Accumulator":
         """A progressive render of params' tile (spt_render_accum): an object
@@ -683,7 +708,7 @@ class Accumulator:
                                    ctypes.byref(st), _stream_handle(stream)), "spt_render_accum")
         self.samples += spp
         self._count_stale = True
-        return st.as_dict()
+        return self.scene.backend._stats(st)
 
     def add_list(self, spp: int, pixels: torch.Tensor, n: Optional[int] = None, stream=None) -> dict:
         """spt_render_accum_list: samples [samples, samples + spp) of the tile
@@ -708,7 +733,7 @@ class Accumulator:
             self.samples += spp
         if n != self.count.numel():
             self.sparse = True
-        return st.as_dict()
+        return self.scene.backend._stats(st)
 
     def add_adaptive(self, spp: int, tolerance: Optional[float] = None, min_spp: Optional[int] = None,
                      max_spp: Optional[int] = None, floor: Optional[float] = None, stream=None) -> dict:
@@ -892,6 +917,26 @@ def read_pfm(path: str) -> np.ndarray:
         return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).copy()
     finally:
         lib.spt_pfm_free(p)
+
+
+def light_table_build(tri_vertices, mat_id, emission_rgb):
+    """spt_light_table_build: (ids uint32, cdf float32, pdf_area float32) of the light
+    table of (T, 9) triangle vertices, T material ids (None: all 0) and (M, 3)
+    emission (None: no emitters).  Host only."""
+    tv = np.ascontiguousarray(np.asarray(tri_vertices, dtype=np.float32).reshape(-1, 9))
+    mat = None if mat_id is None else np.ascontiguousarray(np.asarray(mat_id, dtype=np.int32).reshape(-1))
+    if mat is not None and mat.size != tv.shape[0]:
+        raise ValueError(f"light_table_build: {mat.size} material ids for {tv.shape[0]} triangles")
+    emi = None if emission_rgb is None else np.ascontiguousarray(np.asarray(emission_rgb, dtype=np.float32).reshape(-1, 3))
+    nmat = 0 if emi is None else emi.shape[0]
+    n = ctypes.c_uint32(0)
+    args = (_host_ptr(tv) if tv.size else None, _host_ptr(mat), tv.shape[0], _host_ptr(emi) if nmat else None, nmat)
+    check(lib.spt_light_table_build(*args, None, None, None, 0, ctypes.byref(n)), "spt_light_table_build")
+    ids, cdf, pdf = np.zeros(n.value, np.uint32), np.zeros(n.value, np.float32), np.zeros(n.value, np.float32)
+    if n.value:
+        check(lib.spt_light_table_build(*args, ids.ctypes.data, cdf.ctypes.data, pdf.ctypes.data, n.value,
+                                        ctypes.byref(n)), "spt_light_table_build")
+    return ids, cdf, pdf
 
 
 def envmap_from_latlong(img, n: int) -> np.ndarray:
