@@ -492,6 +492,68 @@ spt_status spt_light_table_build(const float* tri_vertices, const int32_t* mat_i
                                  const float* emission_rgb, uint32_t nmat, uint32_t* ids, float* cdf,
                                  float* pdf_area, uint32_t capacity, uint32_t* n_out);
 
+/* Sky sampling — importance sampling of the sky image with shadow rays
+ * (a build addition), a switch of its own beside
+ * spt_scene_set_light_sampling.  With it on, a sky image set
+ * (spt_scene_set_envmap) and a non-empty table, every diffuse path vertex that
+ * bounces (light sampling's vertex condition) draws a direction from a
+ * distribution proportional to the image's brightness — texel cell (i, j) with
+ * probability proportional to the cell mean of max(|r|, |g|, |b|) times the
+ * cell's solid angle, the point uniformly in the cell of the octahedral square
+ * — and traces one shadow ray that way, an any-hit query over [0.001 / |d|,
+ * inf).  If it meets nothing (no triangle, no analytic sphere) the path
+ * gathers throughput x env x M(d) x p / pdf(d): M the map's lookup as an
+ * escaping ray reads it, p the density with which the bounce sampler itself
+ * sends a ray that way, pdf the sampler's own, evaluated from the traced
+ * direction.  The next ray of that path adds no sky if it escapes (the sample
+ * stood for it); camera rays and rays leaving a mirror or glass vertex read
+ * the sky as always.  The expected image is the one of the switch off.
+ *
+ * Where light sampling is on too (a non-empty light table) a vertex still
+ * traces one shadow ray: toward the sky with probability `share`, the
+ * contribution divided by share, else toward an emissive triangle as light
+ * sampling does, divided by 1 - share; both "the next hit / escape adds
+ * nothing" marks are set whichever was drawn.  Otherwise share is stored and
+ * not used.  The numbers come from a side stream of their own (sky_uniform), so
+ * paths, roulette and ray_casts are those of the switch off; the shadow rays
+ * are counted by spt_scene_get_shadow_casts.
+ *
+ * The table is built on the host in f64 from the map as the scene stores it
+ * (spt_sky_table_build is the same code) and lives on the device beside the
+ * map: (8 n^2 + 4 n + 16) bytes, 134 MB at n = 4096.  On with no map: accepted
+ * and inert; spt_scene_set_envmap while the switch is on builds the table of the
+ * new map (a rebuild that fails turns the switch off and returns the error,
+ * the new map set), removing the map empties it.  An all-zero map has an empty
+ * table: inert, every render bit-equal to the switch off.  With a non-empty
+ * table every render runs the fused pipeline and refuses SPT_FLAG_WAVEFRONT /
+ * SPT_FLAG_TRAVERSAL_STATS, and spt_scene_save refuses the scene, as for light
+ * sampling.  params.env tints the gathered radiance as it tints an escape; it
+ * is not in the table.  Waits for queued renders like the other setters.
+ * SPT_ERR_INVALID: NULL scene, on > 1, share outside (0, 1) or not finite
+ * (checked whatever `on` is), or a map rotation R that is not orthonormal, max
+ * |R R^T - I| > 1e-4 (the sampler turns map directions into the world with
+ * R^T); SPT_ERR_LIMIT: a traversal stack that no longer fits the device's LDS
+ * beside the light-sampling kernels' per-lane records.  The scene is unchanged
+ * after an error.  spt_scene_get_sky_sampling: the switch, the share and the
+ * table's cells (n^2, or 0 for none / empty); any pointer may be NULL. */
+spt_status spt_scene_set_sky_sampling(spt_scene scene, uint32_t on, float share);
+spt_status spt_scene_get_sky_sampling(spt_scene scene, uint32_t* on, float* share, uint32_t* cells);
+
+/* Host only, no device: the sampling table of an n x n octahedral image (n x n
+ * x 3 floats, row j, column i; 1 <= n <= 4096).  In f64: Y = max(|r|, |g|, |b|);
+ * Ybar(i, j) = sum over the 3 x 3 neighbours (octahedral edge rule) of
+ * k(dx) k(dy) Y, k = {1/8, 3/4, 1/8} — the cell mean of the bilinear interpolant;
+ * w = Ybar / |p_c|^3, p_c the octahedron point of the texel centre (not finite
+ * or not positive: 0).  marginal[n]: f32 cdf over rows; conditional[n * n]: a f32
+ * cdf per row; each cdf's last entry is 1, and "the smallest index with xi <
+ * cdf" is the draw.  density[n * n]: f32((w / sum w) n^2 / 4), the density over
+ * the [-1, 1]^2 square that weighs a sample.  *cells_out: n^2, or 0 when sum w
+ * is 0 or not finite (the table is empty and the arrays are not written).  Any
+ * of the three arrays may be NULL.  SPT_ERR_INVALID: NULL rgb or cells_out,
+ * n = 0; SPT_ERR_LIMIT: n > 4096. */
+spt_status spt_sky_table_build(const float* rgb, uint32_t n, float* marginal, float* conditional, float* density,
+                               uint32_t* cells_out);
+
 /* Host only, no device: resample a lat-long image (w x h interleaved RGB, rows
  * top-down; pbrt's convention theta = acos(z), phi = atan2(y, x), u = phi / 2pi
  * wrapped, v = theta / pi clamped, bilinear) to the n x n octahedral texel

@@ -23,6 +23,7 @@
 #include "host_error.h"
 #include "render_plan.h"
 #include "light_table.h"
+#include "sky_table.h"
 #include "scene_state.h"
 #include "spt_internal.h"
 
@@ -767,7 +768,7 @@ spt_status spt_scene_set_config(spt_scene sc, const spt_config* cfg) {
     // (stack_slack stays as built, below: the stack checked is the one the scene has)
     {
         DeviceGuard dg(sc->device);
-        if ((st = check_stack_lds("spt_scene_set_config", sc->stack_depth, sc->cfg.bvh_width, sc->lights != nullptr)))
+        if ((st = check_stack_lds("spt_scene_set_config", sc->stack_depth, sc->cfg.bvh_width, sc->lights != nullptr || sc->sky != nullptr)))
             return st;
     }
     const spt_config old = sc->cfg;
@@ -860,6 +861,47 @@ spt_status spt_scene_set_material_kinds(spt_scene sc, const uint32_t* kinds, uin
     return SPT_OK;
 }
 
+namespace {
+
+// The sampling table of an n x n sky image on the device (sky_table.h; caller
+// has made the device current).  *out: null for an empty table.  The sampler
+// turns a map direction into the world with R^T, so R must be orthonormal:
+// max |R R^T - I| <= 1e-4 in f64 (a rotation rounded to f32 stands near 1e-7).
+spt_status build_sky(const char* what, const float* rgb, uint32_t n, const float* rot, float share, DeviceSky** out,
+                     uint32_t* cells) {
+    *out = nullptr;
+    *cells = 0;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            double s = 0.0;
+            for (int k = 0; k < 3; k++) s += (double)rot[3 * r + k] * (double)rot[3 * c + k];
+            if (!(std::fabs(s - (r == c ? 1.0 : 0.0)) <= 1e-4))
+                return fail(SPT_ERR_INVALID, "%s: the map's rotation is not orthonormal ((R R^T)[%d][%d] = %g): sky "
+                            "sampling turns map directions into the world with its transpose", what, r, c, s);
+        }
+    SkyTable t;
+    sky_table_build(rgb, n, t);
+    if (t.empty()) return SPT_OK;
+    const size_t nn = (size_t)n * n;
+    std::vector<unsigned char> buf(sizeof(DeviceSky) + sizeof(float) * (n + 2 * nn));
+    DeviceSky h{};
+    h.share = share;
+    unsigned char* p = buf.data();
+    std::memcpy(p, &h, sizeof(h));
+    p += sizeof(h);
+    std::memcpy(p, t.marg.data(), sizeof(float) * n);
+    p += sizeof(float) * n;
+    std::memcpy(p, t.cond.data(), sizeof(float) * nn);
+    p += sizeof(float) * nn;
+    std::memcpy(p, t.pdf.data(), sizeof(float) * nn);
+    spt_status us = upload(out, buf.data(), buf.size());
+    if (us) return us;
+    *cells = (uint32_t)nn;
+    return SPT_OK;
+}
+
+}  // namespace
+
 spt_status spt_scene_set_envmap(spt_scene sc, const float* rgb, uint32_t n, const float* rotation) {
     static const char* what = "spt_scene_set_envmap";
     if (!sc) return fail(SPT_ERR_INVALID, "%s: NULL scene", what);
@@ -875,8 +917,23 @@ spt_status spt_scene_set_envmap(spt_scene sc, const float* rgb, uint32_t n, cons
                             (k / 3) / n, k % 3);
     }
     DeviceGuard dg(sc->device);
+    std::lock_guard<std::mutex> lk(sc->mu);
     DeviceEnvMap* d_map = nullptr;
     float4* d_tex = nullptr;
+    // sky sampling on: the table of the new map (a failure turns the switch off
+    // and is returned once the map itself is set)
+    DeviceSky* d_sky = nullptr;
+    uint32_t cells = 0;
+    spt_status sky_st = SPT_OK;
+    static const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (rgb && sc->sky_sampling) {
+        sky_st = build_sky(what, rgb, n, rotation ? rotation : ident, sc->sky_share, &d_sky, &cells);
+        if (!sky_st && d_sky && (sky_st = check_stack_lds(what, sc->stack_depth, sc->cfg.bvh_width, true))) {
+            hfree(d_sky);
+            d_sky = nullptr;
+            cells = 0;
+        }
+    }
     if (rgb) {
         // the image inside its gutter (DeviceEnvMap): gutter texels by the edge rule
         const int32_t ni = (int32_t)n;
@@ -891,28 +948,115 @@ spt_status spt_scene_set_envmap(spt_scene sc, const float* rgb, uint32_t n, cons
             }
         DeviceEnvMap h;
         h.n = n;
-        static const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         std::memcpy(h.rot, rotation ? rotation : ident, sizeof(h.rot));
         spt_status us = upload(&d_tex, tex.data(), sizeof(float4) * tex.size());
         h.texels = d_tex;
+        h.sky = d_sky;
         if (!us) us = upload(&d_map, &h, sizeof(h));
         if (us) {
             hfree(d_tex);
             hfree(d_map);
+            hfree(d_sky);
             return us;
         }
     }
-    std::lock_guard<std::mutex> lk(sc->mu);
     spt_status qs = quiesce_scene(sc);  // queued renders may still read the old map
     if (qs) {
         hfree(d_tex);
         hfree(d_map);
+        hfree(d_sky);
         return qs;
     }
     hfree(sc->envmap);
     hfree(sc->env_texels);
+    hfree(sc->sky);
     sc->envmap = d_map;
     sc->env_texels = d_tex;
+    sc->env_n = rgb ? n : 0;
+    std::memcpy(sc->env_rot, rgb && rotation ? rotation : ident, sizeof(sc->env_rot));
+    sc->sky = d_sky;  // (the map removed: the table is empty, the switch stays)
+    sc->sky_cells = cells;
+    if (sky_st) sc->sky_sampling = false;
+    return sky_st;
+}
+
+spt_status spt_scene_set_sky_sampling(spt_scene sc, uint32_t on, float share) {
+    static const char* what = "spt_scene_set_sky_sampling";
+    if (!sc) return fail(SPT_ERR_INVALID, "%s: NULL scene", what);
+    if (on > 1) return fail(SPT_ERR_INVALID, "%s: on = %u (0 or 1)", what, on);
+    if (!(share > 0.0f && share < 1.0f))
+        return fail(SPT_ERR_INVALID, "%s: share = %g (inside (0, 1))", what, (double)share);
+    DeviceGuard dg(sc->device);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    spt_status st = quiesce_scene(sc);  // queued renders may still read the old table
+    if (st) return st;
+    DeviceSky* d_sky = nullptr;
+    DeviceEnvMap* d_map = nullptr;
+    uint32_t cells = 0;
+    if (sc->envmap) {
+        const uint32_t n = sc->env_n;
+        if (on) {
+            // the texels back from the scene's own gutter array (the host keeps no copy)
+            const size_t pitch = (size_t)n + 2;
+            std::vector<float4> tex(pitch * pitch);
+            HIP_TRY(hipMemcpy(tex.data(), sc->env_texels, sizeof(float4) * tex.size(), hipMemcpyDeviceToHost));
+            std::vector<float> rgb((size_t)n * n * 3);
+            for (uint32_t j = 0; j < n; j++)
+                for (uint32_t i = 0; i < n; i++) {
+                    const float4 t = tex[(size_t)(j + 1) * pitch + (i + 1)];
+                    float* o = &rgb[((size_t)j * n + i) * 3];
+                    o[0] = t.x; o[1] = t.y; o[2] = t.z;
+                }
+            if ((st = build_sky(what, rgb.data(), n, sc->env_rot, share, &d_sky, &cells))) return st;
+            if (d_sky && (st = check_stack_lds(what, sc->stack_depth, sc->cfg.bvh_width, true))) {
+                hfree(d_sky);
+                return st;
+            }
+        }
+        // the map's header again, with the new table (or none) behind it
+        DeviceEnvMap h;
+        h.n = n;
+        std::memcpy(h.rot, sc->env_rot, sizeof(h.rot));
+        h.texels = sc->env_texels;
+        h.sky = d_sky;
+        if ((st = upload(&d_map, &h, sizeof(h)))) {
+            hfree(d_sky);
+            return st;
+        }
+        hfree(sc->envmap);
+        sc->envmap = d_map;
+    }
+    hfree(sc->sky);
+    sc->sky = d_sky;
+    sc->sky_cells = cells;
+    sc->sky_sampling = on != 0;
+    sc->sky_share = share;
+    return SPT_OK;
+}
+
+spt_status spt_scene_get_sky_sampling(spt_scene sc, uint32_t* on, float* share, uint32_t* cells) {
+    if (!sc) return fail(SPT_ERR_INVALID, "spt_scene_get_sky_sampling: NULL scene");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (on) *on = sc->sky_sampling ? 1u : 0u;
+    if (share) *share = sc->sky_share;
+    if (cells) *cells = sc->sky_cells;
+    return SPT_OK;
+}
+
+spt_status spt_sky_table_build(const float* rgb, uint32_t n, float* marginal, float* conditional, float* density,
+                               uint32_t* cells_out) {
+    static const char* what = "spt_sky_table_build";
+    if (!cells_out) return fail(SPT_ERR_INVALID, "%s: NULL cells_out", what);
+    if (!rgb) return fail(SPT_ERR_INVALID, "%s: NULL image", what);
+    if (n == 0) return fail(SPT_ERR_INVALID, "%s: n = 0", what);
+    if (n > kSkyMaxN) return fail(SPT_ERR_LIMIT, "%s: n = %u (at most %u)", what, n, kSkyMaxN);
+    SkyTable t;
+    sky_table_build(rgb, n, t);
+    *cells_out = t.empty() ? 0u : n * n;
+    if (t.empty()) return SPT_OK;
+    if (marginal) std::memcpy(marginal, t.marg.data(), sizeof(float) * n);
+    if (conditional) std::memcpy(conditional, t.cond.data(), sizeof(float) * t.cond.size());
+    if (density) std::memcpy(density, t.pdf.data(), sizeof(float) * t.pdf.size());
     return SPT_OK;
 }
 

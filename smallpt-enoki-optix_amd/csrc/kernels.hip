@@ -1509,14 +1509,24 @@ __global__ __launch_bounds__(kIsectBlock) void aov_kernel(AovArgs a) {
 // path's rays, hits, roulette and throughput are those of the other
 // instances.  park[1].z carries the path's "the next triangle hit drops its
 // emission" bit.
+//
+// kSky (with kNee and kEnv): the scene samples its sky image
+// (DeviceEnvMap::sky).  The same machinery: a diffuse vertex
+// parks its bounce ray and traces one shadow ray — toward a direction drawn
+// from the sky's table (an any-hit query without a far end; the parked light
+// id is kSkyLightId and the contribution joins if the ray met nothing), or,
+// where the scene samples its triangles too (a.sc.lights), toward one of them
+// with probability 1 - share.  Bit 1 of park[1].z: "the next escape adds no
+// sky"; bit 0 (the triangles' bit) is set only where the triangles are sampled.
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
-          bool kNee = false>
+          bool kNee = false, bool kSky = false>
 __global__ __launch_bounds__(kIsectBlock)
 __attribute__((amdgpu_waves_per_eu(kDrain && kMode == kModeUnit ? (kNt ? SPT_DRAIN_WAVES_NT : SPT_DRAIN_WAVES)
                                    : kDrain ? SPT_DRAIN_WAVES_RGB : SPT_FUSED_WAVES, 8)))
 void render_fused_kernel(FusedArgs a) {
     constexpr bool kEmit = kMode == kModeEmit;
     static_assert(!kNee || (kEmit && !kDrain), "light sampling: emitter mode, not the drain");
+    static_assert(!kSky || (kNee && kEnv), "sky sampling: the light-sampling lane loop of a scene with a sky image");
 #if SPT_WAVE_LOG
     const unsigned long long wl_t0 = (unsigned long long)wall_clock64();
 #endif
@@ -1558,6 +1568,7 @@ void render_fused_kernel(FusedArgs a) {
                                : nullptr;
     bool busy = false, pending = false;
     bool shadow = false;  // kNee: the ray this lane traces is a shadow ray
+    bool skyray = false;  // kSky: ... toward the sky (any hit occludes)
     uint32_t casts = 0, conts = 0, starts = 0;  // wave-uniform
     uint32_t shadows = 0;                       // kNee: shadow rays traced (wave-uniform)
     // wave-uniform work pool: static share, then dynamic chunks.  XCD-aware
@@ -1607,11 +1618,16 @@ void render_fused_kernel(FusedArgs a) {
                     TraceHit sh = tr.hit(a.sc, L);
                     if (a.sc.nsph) {
                         float tmn, tmx;
-                        light_shadow_interval(dir, tmn, tmx);
-                        trace_spheres(a.sc, tr.o, dir, tmn, false, sh);
+                        light_shadow_interval(dir, tmn, tmx);  // (the sky's interval starts at the same tmin)
+                        trace_spheres(a.sc, tr.o, dir, tmn, kSky && skyray, sh);
                     }
                     const float4 p2 = park[2], p3 = park[3];
-                    if (sh.slot >= 0 && sh.id == f2u(p3.z)) {
+                    bool vis = sh.slot >= 0 && sh.id == f2u(p3.z);
+                    if constexpr (kSky) {  // the sky is seen iff the ray met nothing
+                        if (skyray) vis = sh.slot == -1;
+                        skyray = false;
+                    }
+                    if (vis) {
                         const float4 p0 = park[0], p1 = park[1];
                         park[0] = make_float4(p0.x, p0.y, p0.z, p0.w + p2.w);
                         park[1] = make_float4(p1.x + p3.x, p1.y + p3.y, p1.z, 0.0f);
@@ -1643,15 +1659,18 @@ void render_fused_kernel(FusedArgs a) {
                             const V3 m = env_radiance(a.sc, dir);
                             er = er * m.x; eg = eg * m.y; eb = eb * m.z;
                         }
-                        lr = lr + thr * er;                        // main.cpp:407
-                        lg = lg + thg * eg;
-                        lb = lb + thb * eb;
+                        // (kSky: the last vertex's sky sample stood for this escape)
+                        if (!(kSky && (nee_prev & 2u))) {
+                            lr = lr + thr * er;                    // main.cpp:407
+                            lg = lg + thg * eg;
+                            lb = lb + thb * eb;
+                        }
                     }
                 } else {
                     const float4 m0 = sph ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : a.sc.snrm[(size_t)slot * 3];
                     uint32_t mat = sph ? (a.sc.sph_mat ? (uint32_t)a.sc.sph_mat[-2 - slot] : 0u) : f2u(m0.w);
                     // (kNee: an emissive triangle the last vertex could have sampled adds nothing)
-                    if (kEmit && mat < a.sc.nemit && !(kNee && nee_prev && !sph)) {
+                    if (kEmit && mat < a.sc.nemit && !(kNee && (kSky ? (nee_prev & 1u) : nee_prev) && !sph)) {
                         lr = lr + thr * a.sc.emission[mat * 3];
                         lg = lg + thg * a.sc.emission[mat * 3 + 1];
                         lb = lb + thb * a.sc.emission[mat * 3 + 2];
@@ -1716,10 +1735,38 @@ void render_fused_kernel(FusedArgs a) {
                                         }
                                         V3 sd, sc3;
                                         uint32_t lid;
-                                        if (light_sample(a.sc.lights, hp, nh, v3(thr, thg, thb),
-                                                         light_uniform(gpix, sample, depth, 0u),
-                                                         light_uniform(gpix, sample, depth, 1u),
-                                                         light_uniform(gpix, sample, depth, 2u), sd, sc3, lid)) {
+                                        bool traced;
+                                        if constexpr (kSky) {
+                                            // one shadow ray: the sky with probability share where the
+                                            // triangles are sampled too, always otherwise
+                                            const bool both = a.sc.lights != nullptr;
+                                            const float share = a.sc.envmap->sky->share;
+                                            nee_prev = both ? 3u : 2u;
+                                            float wsel = 1.0f;
+                                            if (!both || sky_uniform(gpix, sample, depth, 4u) < share) {
+                                                traced = sky_sample(a.sc, nh, v3(thr, thg, thb), v3(a.env_r, a.env_g, a.env_b),
+                                                                    sky_uniform(gpix, sample, depth, 0u),
+                                                                    sky_uniform(gpix, sample, depth, 1u),
+                                                                    sky_uniform(gpix, sample, depth, 2u),
+                                                                    sky_uniform(gpix, sample, depth, 3u), sd, sc3);
+                                                lid = kSkyLightId;
+                                                skyray = traced;
+                                                wsel = share;
+                                            } else {
+                                                traced = light_sample(a.sc.lights, hp, nh, v3(thr, thg, thb),
+                                                                      light_uniform(gpix, sample, depth, 0u),
+                                                                      light_uniform(gpix, sample, depth, 1u),
+                                                                      light_uniform(gpix, sample, depth, 2u), sd, sc3, lid);
+                                                wsel = 1.0f - share;
+                                            }
+                                            if (both) sc3 = v3(sc3.x / wsel, sc3.y / wsel, sc3.z / wsel);
+                                        } else {
+                                            traced = light_sample(a.sc.lights, hp, nh, v3(thr, thg, thb),
+                                                                  light_uniform(gpix, sample, depth, 0u),
+                                                                  light_uniform(gpix, sample, depth, 1u),
+                                                                  light_uniform(gpix, sample, depth, 2u), sd, sc3, lid);
+                                        }
+                                        if (traced) {
                                             park[2] = make_float4(dir.x, dir.y, dir.z, sc3.x);
                                             park[3] = make_float4(sc3.y, sc3.z, u2f(lid), 0.0f);
                                             dir = sd;
@@ -1854,7 +1901,9 @@ void render_fused_kernel(FusedArgs a) {
                 if constexpr (kNee) {  // a shadow ray: the closest hit over its own interval
                     float tmn = kRayTmin, tmx = kRayTmax;
                     if (shadow) light_shadow_interval(dir, tmn, tmx);
-                    tr.init(a.sc, tr.o, dir, tmn, tmx, false, L);
+                    if constexpr (kSky)
+                        if (skyray) sky_shadow_interval(dir, tmn, tmx);
+                    tr.init(a.sc, tr.o, dir, tmn, tmx, kSky && skyray, L);
                 } else {
                     tr.init(a.sc, tr.o, dir, kRayTmin, kRayTmax,
                             (meta & ((1u << kMetaDepthBits) - 1u)) + 1u >= a.max_depth && !kEmit, L);
@@ -2458,7 +2507,7 @@ hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipSt
 }
 
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
-          bool kNee = false>
+          bool kNee = false, bool kSky = false>
 static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
     static thread_local size_t cached_lds = 0;
     static thread_local uint32_t cached = 0;
@@ -2471,7 +2520,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     (void)hipGetDevice(&dev);
     if (!cached || cached_lds != lds || cached_dev != dev) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee>,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky>,
                                                          kIsectBlock, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -2484,7 +2533,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     // (the drain's grid cannot follow its count, which is on the device)
     const uint32_t blocks = kDrain ? scaled : min(scaled, blocks_for(a.count > 0 ? a.count : 1, kIsectBlock));
     if (lanes_out) *lanes_out = blocks * kIsectBlock;
-    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee>), dim3(blocks), dim3(kIsectBlock),
+    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky>), dim3(blocks), dim3(kIsectBlock),
                        lds, s, a);
     return hipGetLastError();
 }
@@ -2493,11 +2542,14 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false>
 static hipError_t launch_fused_e(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
     // a scene with a light table takes the kNee instance (emitter mode, never the drain: the plan)
-    if constexpr (kMode == kModeEmit && !kDrain && !kNt)
+    if constexpr (kMode == kModeEmit && !kDrain && !kNt) {
+        // a scene that samples its sky image (with or without a light table): the kSky instance
+        if (a.sc.sky && a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true, true>(a, s, lanes_out);
         if (a.sc.lights) {
             if (a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true>(a, s, lanes_out);
             return launch_fused_t<Tr, kMode, kDrain, kNt, kList, false, true>(a, s, lanes_out);
         }
+    }
     if constexpr (kMode != kModeUnit)
         if (a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true>(a, s, lanes_out);
     return launch_fused_t<Tr, kMode, kDrain, kNt, kList>(a, s, lanes_out);

@@ -23,6 +23,7 @@
 //                  [--aov PREFIX] [--denoise [--denoise-iters N]]
 //                  [--passes N] [--variance FILE] [--denoise-var]
 //                  [--envmap sky.pfm [--env-res N] | --envmap-oct sky.pfm] [--env-rotate-y DEG] [--nee]
+//                  [--sky-nee [--sky-share X]]
 //
 // --aov PREFIX writes the first-hit buffers of the render (spt_render_aov) as
 // PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm (depth in all three
@@ -53,6 +54,12 @@
 // the same reason.  It works with every other flag, --gpus included: each
 // rank builds the same table from the same triangles, and the side stream is
 // keyed by the global pixel.
+//
+// --sky-nee switches sky sampling on (spt_scene_set_sky_sampling: a shadow ray
+// toward a direction drawn from the sky image's brightness at every diffuse
+// vertex); it needs --envmap or --envmap-oct and is refused without one.
+// --sky-share X (default 0.5, inside (0, 1)) is the probability of the sky
+// where --nee samples the emissive triangles too.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -247,6 +254,8 @@ int main(int argc, char** argv) {
     int env_res = 512;
     double env_rotate_y = 0.0;  // degrees
     bool nee = false;           // --nee: spt_scene_set_light_sampling
+    bool sky_nee = false, set_sky_share = false;  // --sky-nee: spt_scene_set_sky_sampling
+    float sky_share = 0.5f;     // --sky-share
     int denoise_iters = -1;  // -1: spt_default_denoise_params
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
@@ -288,6 +297,8 @@ int main(int argc, char** argv) {
         else if (a == "--env-res") env_res = std::atoi(next());
         else if (a == "--env-rotate-y") { env_rotate_y = std::atof(next()); env_rotate = true; }
         else if (a == "--nee") nee = true;
+        else if (a == "--sky-nee") sky_nee = true;
+        else if (a == "--sky-share") { sky_share = (float)std::atof(next()); set_sky_share = true; }
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
     }
@@ -320,6 +331,14 @@ int main(int argc, char** argv) {
     }
     if (!envmap_in.empty() && (ngpu > 1 || env_res < 1 || env_res > 4096 || !std::isfinite(env_rotate_y))) {
         std::cerr << "--envmap renders on one device (not with --gpus above 1); --env-res takes 1..4096\n";
+        return 2;
+    }
+    if (sky_nee && envmap_in.empty()) {
+        std::cerr << "--sky-nee samples the sky image: it goes with --envmap / --envmap-oct\n";
+        return 2;
+    }
+    if ((set_sky_share && !sky_nee) || !(sky_share > 0.0f && sky_share < 1.0f)) {
+        std::cerr << "--sky-share takes a number inside (0, 1) and goes with --sky-nee\n";
         return 2;
     }
     if (do_denoise && do_denoise_var) {
@@ -376,6 +395,7 @@ int main(int argc, char** argv) {
             }
         }
         if (nee && ngpu < 1) scene.set_light_sampling();  // after the save: the cache does not store the switch
+        if (sky_nee) scene.set_sky_sampling(true, sky_share);  // (a map renders on one device: this scene)
         if (pi.has_camera) {
             p.camera = pi.camera;
             if (!set_w) p.width = pi.xres;

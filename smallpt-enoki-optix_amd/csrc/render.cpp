@@ -748,13 +748,15 @@ RenderPlanIn plan_inputs(const spt_scene_t* sc, const spt_render_params& p, uint
     // (every albedo 1, no emitters) needs only the ray and an escaped flag.
     // (a sky image needs radiance in the film slots: an escaped flag cannot carry it)
     const bool unit = sc->albedo_unit && sc->ntex == 0 && sc->nsph == 0 && sc->nkind == 0 && !sc->envmap;
-    in.mode = sc->emission ? kModeEmit : (unit ? kModeUnit : kModeAlbedo);
+    // (a scene that samples its sky takes the emitter-mode instances, the only ones
+    // with the light-sampling lane loop, with or without an emission table)
+    in.mode = sc->emission || sc->sky ? kModeEmit : (unit ? kModeUnit : kModeAlbedo);
     in.planes = mode_planes(in.mode);
     in.film_unit = mode_film_bytes(in.mode);
     in.device_bytes = sc->stats.device_bytes;
     in.nsph = sc->nsph;
     in.wide_nodes = sc->nodes8 != nullptr;
-    in.nee = sc->lights != nullptr;
+    in.nee = sc->lights != nullptr || sc->sky != nullptr;
     in.null_caller = caller == nullptr || caller == hipStreamLegacy || caller == hipStreamPerThread;
     if (const WorkSet* hs = sc->ws.bound_set(caller)) {
         for (int k = 0; k < kMaxStreams; k++) {
@@ -1365,6 +1367,9 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
     if (sc->lights && (p.flags & (SPT_FLAG_WAVEFRONT | SPT_FLAG_TRAVERSAL_STATS)))
         return fail(SPT_ERR_INVALID, "spt_render: SPT_FLAG_WAVEFRONT / SPT_FLAG_TRAVERSAL_STATS on a scene with light "
                     "sampling on (it runs in the fused pipeline only; spt_scene_set_light_sampling(scene, 0) first)");
+    if (sc->sky && (p.flags & (SPT_FLAG_WAVEFRONT | SPT_FLAG_TRAVERSAL_STATS)))
+        return fail(SPT_ERR_INVALID, "spt_render: SPT_FLAG_WAVEFRONT / SPT_FLAG_TRAVERSAL_STATS on a scene with sky "
+                    "sampling on (it runs in the fused pipeline only; spt_scene_set_sky_sampling(scene, 0, 0.5f) first)");
     RenderSlot* slot = nullptr;
     if ((st = render_slot(sc->ws, &slot))) return st;
     spt_render_stats& rs = slot->rs;

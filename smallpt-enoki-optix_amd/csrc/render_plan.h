@@ -77,7 +77,8 @@ struct RenderPlanIn {
     // the scene samples its emissive triangles (spt_scene_set_light_sampling with
     // a non-empty table): only the fused lane loop has that estimator, so the
     // plan is the fused pipeline whatever spt_config.pipeline, the flags and the
-    // job size say (the render refuses SPT_FLAG_WAVEFRONT / _TRAVERSAL_STATS first)
+    // job size say (the render refuses SPT_FLAG_WAVEFRONT / _TRAVERSAL_STATS first).
+    // Likewise a scene that samples its sky image (spt_scene_set_sky_sampling, §15).
     bool nee = false;
     // the caller renders on a null stream (legacy or per-thread)
     bool null_caller = false;

@@ -303,6 +303,9 @@ spt_status spt_scene_save(spt_scene sc, const char* path, const void* extra, uin
     if (sc->light_sampling)  // likewise: the file would come back with another estimator
         return fail(SPT_ERR_INVALID, "%s: the scene has light sampling on, which the cache does not store "
                     "(spt_scene_set_light_sampling(scene, 0), save, and switch it on again after loading)", what);
+    if (sc->sky_sampling)
+        return fail(SPT_ERR_INVALID, "%s: the scene has sky sampling on, which the cache does not store "
+                    "(spt_scene_set_sky_sampling(scene, 0, 0.5f), save, and switch it on again after loading)", what);
     CacheHeader h;
     std::memset(&h, 0, sizeof(h));
     std::memcpy(h.magic, kCacheMagic, 8);

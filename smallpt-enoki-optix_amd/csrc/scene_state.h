@@ -91,6 +91,14 @@ struct spt_scene_t {
     // the sky image (spt_scene_set_envmap): the device struct and the texels behind it
     spt::DeviceEnvMap* envmap = nullptr;
     float4* env_texels = nullptr;
+    uint32_t env_n = 0;  // the map's size and rotation as set (the sky table is built from them)
+    float env_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    // sky sampling (spt_scene_set_sky_sampling): the switch, the share, and the
+    // table behind envmap->sky (null: off, no map, or an empty table)
+    bool sky_sampling = false;
+    float sky_share = 0.5f;
+    spt::DeviceSky* sky = nullptr;
+    uint32_t sky_cells = 0;
     // light sampling (spt_scene_set_light_sampling): the switch, and the table
     // built from the scene's emissive triangles (null: off, or an empty table)
     bool light_sampling = false;
@@ -116,6 +124,7 @@ struct spt_scene_t {
         d.spheres = spheres; d.sph_mat = sph_mat; d.nsph = nsph;
         d.mat_kind = mat_kind; d.nkind = nkind;
         d.envmap = envmap;
+        d.sky = sky != nullptr;
         d.lights = lights;
         return d;
     }
@@ -125,7 +134,7 @@ struct spt_scene_t {
         spt::workspace_release(ws);
         spt::hfree(nodes); spt::hfree(nodes8); spt::hfree(emission); spt::hfree(tris); spt::hfree(snrm); spt::hfree(tc); spt::hfree(orig2slot); spt::hfree(albedo);
         spt::hfree(tex_info); spt::hfree(texels); spt::hfree(spheres); spt::hfree(sph_mat); spt::hfree(mat_kind);
-        spt::hfree(envmap); spt::hfree(env_texels);
+        spt::hfree(envmap); spt::hfree(env_texels); spt::hfree(sky);
         spt::hfree(lights);
         spt::refit_plan_release(refit);
         spt::hfree(refit_bad);

@@ -125,6 +125,10 @@ class Scene {
     void set_light_sampling(bool on = true) {
         check(spt_scene_set_light_sampling(scene_, on ? 1u : 0u), "spt_scene_set_light_sampling");
     }
+    // spt_scene_set_sky_sampling: importance sampling of the sky image with shadow rays
+    void set_sky_sampling(bool on = true, float share = 0.5f) {
+        check(spt_scene_set_sky_sampling(scene_, on ? 1u : 0u, share), "spt_scene_set_sky_sampling");
+    }
     spt_refit_stats refit_stats() const {
         spt_refit_stats st{};
         check(spt_scene_get_refit_stats(scene_, &st), "spt_scene_get_refit_stats");

@@ -102,9 +102,12 @@ struct DeviceScene {
     uint32_t nsph;
     const uint32_t* mat_kind;  // per material SPT_MAT_* (null: every material diffuse)
     uint32_t nkind;
+    uint32_t sky;  // the map behind envmap holds a sampling table (DeviceEnvMap::sky; in the padding: the struct does not grow)
     const DeviceEnvMap* envmap;  // the sky image (spt_scene_set_envmap; null: the constant params.env)
     const DeviceLights* lights;  // the light table (spt_scene_set_light_sampling; null: off, or an empty table)
 };
+
+static_assert(sizeof(DeviceScene) == 176, "the kernel arguments do not grow (the drain spills SGPRs, DESIGN.md §8)");
 
 // The environment map on the device: an octahedral image of
 // n x n RGB texels inside a one-texel gutter, so texel (i, j), i and j in
@@ -112,10 +115,12 @@ struct DeviceScene {
 // across the octahedral edge (envmap_wrap), filled when the map is set, so the
 // lookup is a plain bilinear fetch.  One pointer in DeviceScene: the kernel
 // arguments do not grow by the rotation.
+struct DeviceSky;
 struct DeviceEnvMap {
     uint32_t n;
     float rot[9];          // row-major, world -> map
     const float4* texels;  // (n + 2)^2, w unused
+    const DeviceSky* sky;  // the sampling table (spt_scene_set_sky_sampling; null: off, or an empty table)
 };
 constexpr uint32_t kEnvMapMaxN = 4096;
 
@@ -229,6 +234,79 @@ SPT_HD bool light_sample(const DeviceLights* lt, V3 x, V3 nf, V3 T, float xi0, f
     if (!(cx > 0.0f) || !(cy > 0.0f) || !(g < INFINITY)) return false;
     c = v3((T.x * q3.x) * g, (T.y * q3.y) * g, (T.z * q3.z) * g);
     return c.x != 0.0f || c.y != 0.0f || c.z != 0.0f;
+}
+
+// The sky image's sampling table on the device (sky_table.h):
+// one allocation behind DeviceEnvMap::sky — this header, then the n floats of
+// the row marginal cdf, the n * n of the per-row conditional cdfs and the
+// n * n of the density plane (n = DeviceEnvMap::n).
+struct DeviceSky {
+    float share;  // the probability of sampling the sky where the scene samples its triangles too
+    uint32_t pad[3];
+};
+SPT_HD const float* sky_marg(const DeviceSky* s) { return (const float*)(s + 1); }
+constexpr uint32_t kSkyLightId = 0xffffffffu;  // the parked light id of a sky shadow ray
+
+// The smallest index with xi < cdf[i] (the last entry is 1 > xi).
+SPT_HD uint32_t sky_search(const float* cdf, uint32_t n, float xi) {
+    uint32_t lo = 0, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (xi < cdf[mid]) hi = mid;
+        else lo = mid + 1u;
+    }
+    return lo;
+}
+
+// sky_pdf(d): the solid-angle density with which sky_sample sends a ray in
+// the traced world direction d (spt_math.h sky_density over the scene's table).
+SPT_HD float sky_pdf(const DeviceScene& sc, V3 d) {
+    const DeviceEnvMap& m = *sc.envmap;
+    return sky_density(m.n, m.rot, sky_marg(m.sky) + m.n + (size_t)m.n * m.n, d);
+}
+
+// Sky sampling at a diffuse path vertex: row j from xi0 (the
+// marginal), column i from xi1 (row j's conditional), the point (a, b) of the
+// octahedral square inside that cell from xi2, xi3, unfolded to p on the
+// octahedron and turned into the world, d = R^T p (un-normalised) — the shadow
+// ray's direction, any hit over [kRayTmin rl, inf) occluding, rl = 1 / |d|.
+// The contribution the path gathers if the ray meets nothing:
+//   c = (T (env M(d))) g,  g = cx / (pi sky_pdf(d)),  M(d) = env_radiance(d)
+// with cx pi times the bounce sampler's own density toward d (light_sample's
+// cx, of the normal nf as the sampler takes it).  False: no shadow ray (cx or
+// the density not positive, g not finite, or c = 0 in every channel).  f32,
+// every operation rounded, in this order: tests/sky_ref.py restates it.
+SPT_HD bool sky_sample(const DeviceScene& sc, V3 nf, V3 T, V3 env, float xi0, float xi1, float xi2, float xi3, V3& d,
+                       V3& c) {
+    const DeviceEnvMap& m = *sc.envmap;
+    const float* marg = sky_marg(m.sky);
+    const uint32_t j = sky_search(marg, m.n, xi0);
+    const uint32_t i = sky_search(marg + m.n + (size_t)j * m.n, m.n, xi1);
+    const float fn = (float)m.n;
+    const float a = (((float)i + xi2) / fn) * 2.0f - 1.0f;
+    const float b = (((float)j + xi3) / fn) * 2.0f - 1.0f;
+    const V3 p = sky_unfold(a, b);
+    d = v3((m.rot[0] * p.x + m.rot[3] * p.y) + m.rot[6] * p.z, (m.rot[1] * p.x + m.rot[4] * p.y) + m.rot[7] * p.z,
+           (m.rot[2] * p.x + m.rot[5] * p.y) + m.rot[8] * p.z);
+    c = v3(0.0f, 0.0f, 0.0f);
+    const float rl = 1.0f / sqrtf(dot(d, d));
+    const Frame fr = frame_from_normal(nf);
+    const V3 c1 = cross(fr.by, fr.bz), c2 = cross(fr.bz, fr.bx), c3 = cross(fr.bx, fr.by);
+    const float det = dot(fr.bx, c1);
+    const V3 v = v3(dot(d, c1), dot(d, c2), dot(d, c3));
+    const float vv = dot(v, v);
+    const float cx = ((v.y * det) * fabsf(det)) / ((vv * vv) * ((rl * rl) * rl));
+    const float pdf = sky_pdf(sc, d);
+    const float g = cx / (kPi * pdf);
+    if (!(cx > 0.0f) || !(pdf > 0.0f) || !(g < INFINITY)) return false;
+    const V3 M = env_radiance(sc, d);
+    c = v3((T.x * (env.x * M.x)) * g, (T.y * (env.y * M.y)) * g, (T.z * (env.z * M.z)) * g);
+    return c.x != 0.0f || c.y != 0.0f || c.z != 0.0f;
+}
+// a sky shadow ray's interval: the path rays' offset at the origin, no far end
+SPT_HD void sky_shadow_interval(V3 d, float& tmin, float& tmax) {
+    tmin = kRayTmin * (1.0f / sqrtf(dot(d, d)));
+    tmax = INFINITY;
 }
 
 constexpr uint32_t kMatDiffuse = 0, kMatMirror = 1, kMatGlass = 2;  // SPT_MAT_*

@@ -433,6 +433,55 @@ SPT_HD float light_uniform(uint32_t pixel, uint32_t sample, uint32_t depth, uint
     return (float)(h >> 8) * (1.0f / 16777216.0f);
 }
 
+// The sky-sampling side stream: number k = 0 .. 4 of the vertex
+// a path (pixel, sample) reaches at cast `depth`.  The shape of rr_uniform and
+// light_uniform with constants of its own (five keys per cast, so no key of
+// one cast is a key of the next), keyed by the global pixel and the absolute
+// sample; neither the PCG32 draws, the roulette nor light_uniform move.
+SPT_HD float sky_uniform(uint32_t pixel, uint32_t sample, uint32_t depth, uint32_t k) {
+    uint32_t h = pixel * 0xB5297A4Du ^ (sample + 0x68E31DA4u) * 0x1B56C4E9u ^ (depth * 5u + k + 1u) * 0xA3D8F1C7u;
+    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+    return (float)(h >> 8) * (1.0f / 16777216.0f);
+}
+
+// Octahedral square -> the L1 octahedron (|x| + |y| + |z| = 1 up to rounding):
+// the inverse of the environment map's lookup coordinates.
+// |a| + |b| <= 1 is the upper hemisphere as it is; outside it the lower
+// hemisphere's fold is undone, and z = (1 - |a|) - |b| is negative there.
+SPT_HD V3 sky_unfold(float a, float b) {
+    const float fa = fabsf(a), fb = fabsf(b);
+    const float z = (1.0f - fa) - fb;
+    if (fa + fb <= 1.0f) return v3(a, b, z);
+    return v3((1.0f - fb) * (a < 0.0f ? -1.0f : 1.0f), (1.0f - fa) * (b < 0.0f ? -1.0f : 1.0f), z);
+}
+
+// Solid-angle density of the sky sampler in the traced world
+// direction d (any length): e = R d, s, (a, b) and the fold exactly as
+// env_radiance computes them, the cell of (a, b) clamped into [0, n), and
+// pdf[cell] — the stored density over the [-1, 1]^2 square — times (|e| / s)^3,
+// the square's area per solid angle there.  0 where the lookup reads no sky.
+SPT_HD float sky_density(uint32_t n, const float* rot, const float* pdf, V3 d) {
+    const float ex = (rot[0] * d.x + rot[1] * d.y) + rot[2] * d.z;
+    const float ey = (rot[3] * d.x + rot[4] * d.y) + rot[5] * d.z;
+    const float ez = (rot[6] * d.x + rot[7] * d.y) + rot[8] * d.z;
+    const float s = (fabsf(ex) + fabsf(ey)) + fabsf(ez);
+    if (!(s > 0.0f && s < INFINITY)) return 0.0f;
+    float a = ex / s, b = ey / s;
+    if (ez < 0.0f) {
+        const float fa = (1.0f - fabsf(b)) * (a < 0.0f ? -1.0f : 1.0f);
+        const float fb = (1.0f - fabsf(a)) * (b < 0.0f ? -1.0f : 1.0f);
+        a = fa;
+        b = fb;
+    }
+    const float fn = (float)n;
+    const float fi = floorf((a * 0.5f + 0.5f) * fn), fj = floorf((b * 0.5f + 0.5f) * fn);
+    const int32_t hi = (int32_t)n - 1;
+    const int32_t i = (int32_t)fi < 0 ? 0 : ((int32_t)fi > hi ? hi : (int32_t)fi);
+    const int32_t j = (int32_t)fj < 0 ? 0 : ((int32_t)fj > hi ? hi : (int32_t)fj);
+    const float r = sqrtf((ex * ex + ey * ey) + ez * ez) / s;
+    return pdf[(size_t)j * n + (size_t)i] * ((r * r) * r);
+}
+
 // Heitz's low-distortion map of the unit square to barycentrics (no sqrt):
 // the point is (1 - b1 - b2) v0 + b1 v1 + b2 v2.
 SPT_HD void light_tri_map(float xi1, float xi2, float& b1, float& b2) {

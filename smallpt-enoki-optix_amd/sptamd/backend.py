@@ -255,6 +255,20 @@ class HipBackend:
               "spt_scene_get_light_sampling")
         return bool(on.value), int(n.value)
 
+    def set_sky_sampling(self, on=True, share=0.5) -> None:
+        """spt_scene_set_sky_sampling: sample the sky image (set_envmap) by its
+        brightness with a shadow ray at every diffuse path vertex.  share: the
+        probability of the sky where set_light_sampling is on too.  Renders of such
+        a scene run the fused pipeline; stats["shadow_casts"] counts the rays."""
+        check(lib.spt_scene_set_sky_sampling(self._scene, 1 if on else 0, float(share)), "spt_scene_set_sky_sampling")
+
+    def sky_sampling(self):
+        """(on, share, cells): the switch, the share and the cells of the sky table (0: none or empty)."""
+        on, share, n = ctypes.c_uint32(0), ctypes.c_float(0), ctypes.c_uint32(0)
+        check(lib.spt_scene_get_sky_sampling(self._scene, ctypes.byref(on), ctypes.byref(share), ctypes.byref(n)),
+              "spt_scene_get_sky_sampling")
+        return bool(on.value), float(share.value), int(n.value)
+
     def set_texture(self, material: int, image=None) -> None:
         """Material `material`'s reflectance image (ImageTexture, main.cpp:34-80):
         (H, W, 3) float32, or None to remove it."""
@@ -937,6 +951,23 @@ def light_table_build(tri_vertices, mat_id, emission_rgb):
         check(lib.spt_light_table_build(*args, ids.ctypes.data, cdf.ctypes.data, pdf.ctypes.data, n.value,
                                         ctypes.byref(n)), "spt_light_table_build")
     return ids, cdf, pdf
+
+
+def sky_table_build(image):
+    """spt_sky_table_build: (marginal (N,), conditional (N, N), density (N, N)) float32 of
+    the sampling table of an (N, N, 3) octahedral sky image; three empty arrays for an
+    empty table (a map whose weights sum to 0).  Host only."""
+    img = np.ascontiguousarray(np.asarray(image, dtype=np.float32))
+    if img.ndim != 3 or img.shape[0] != img.shape[1] or img.shape[2] != 3:
+        raise ValueError(f"sky_table_build: the image must be (N, N, 3), got {img.shape}")
+    n = img.shape[0]
+    marg, cond, pdf = np.zeros(n, np.float32), np.zeros((n, n), np.float32), np.zeros((n, n), np.float32)
+    cells = ctypes.c_uint32(0)
+    check(lib.spt_sky_table_build(img.ctypes.data if n else None, n, marg.ctypes.data, cond.ctypes.data, pdf.ctypes.data,
+                                  ctypes.byref(cells)), "spt_sky_table_build")
+    if cells.value == 0:
+        return np.zeros(0, np.float32), np.zeros((0, 0), np.float32), np.zeros((0, 0), np.float32)
+    return marg, cond, pdf
 
 
 def envmap_from_latlong(img, n: int) -> np.ndarray:
