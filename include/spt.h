@@ -539,6 +539,49 @@ spt_status spt_light_table_build(const float* tri_vertices, const int32_t* mat_i
 spt_status spt_scene_set_sky_sampling(spt_scene scene, uint32_t on, float share);
 spt_status spt_scene_get_sky_sampling(spt_scene scene, uint32_t* on, float* share, uint32_t* cells);
 
+/* Multiple importance sampling between the shadow rays of the two switches
+ * above and the bounce rays, a third per-scene switch, off by
+ * default and independent of the order in which the three switches, the
+ * emission and the map are set.  Light and sky sampling *replace* the bounce
+ * ray's view of the lights they sample: the next hit on an emissive triangle,
+ * the next escape into the sky, adds nothing.  That is wrong for a light that
+ * is large or close (the area sampler's weight is unbounded as the distance
+ * goes to 0) and for a sky that is broad (the table ignores the cosine).  With
+ * the switch on the two are combined with the balance heuristic instead.  In
+ * "pi x solid-angle density" units, with p the density with which the bounce
+ * sampler sends a ray in a direction, l the light sampler's there (pdfA r^2 /
+ * |cos'|), k the sky sampler's, and s the probability with which the vertex
+ * chose that sampler (1 with one non-empty table; share for the sky and
+ * 1 - share for the triangles with both):
+ *   a shadow ray toward a triangle carries  throughput x Le x p / (p + s l)
+ *   a shadow ray toward the sky carries     throughput x env x M(d) x p / (p + s k)
+ *   the next hit on an emissive triangle adds its emission x p / (p + s l),
+ *     l from the hit triangle's own record of the light table
+ *   the next escape adds the sky x p / (p + s k)
+ * and nothing is divided by share afterwards.  No ray is added or removed:
+ * paths, roulette, ray_casts and continuations are those of the switch off,
+ * the shadow rays those of the samplers (one whose factor underflows to 0 is
+ * not traced: spt_scene_get_shadow_casts may count a few fewer).  Camera rays,
+ * rays leaving a mirror or glass vertex, emissive spheres and a sky constant
+ * without an image count in full as they do without it.  Degenerate weights:
+ * a hit or escape the sampler cannot produce counts in full — p not positive,
+ * a triangle the table does not hold or never draws (pdfA = 0), one seen
+ * edge-on (cos' = 0), a sky density of 0, or s l (s k) zero or NaN; a sum p +
+ * s l that is not finite gives the hit weight 0 (and the shadow ray factor 0:
+ * not traced); a shadow ray whose s l (s k) is zero or NaN is not traced.
+ * The expected image is the one of the switch off.
+ *
+ * The switch matters only where light or sky sampling acts: with both tables
+ * empty (or both switches off) every render is bit-equal to the switch off
+ * and runs the same kernels.  It survives the table rebuilds of
+ * spt_scene_set_emission, spt_scene_update_geometry and spt_scene_set_envmap.
+ * The scene cache does not store it, and spt_scene_save is not refused on its
+ * account (the two samplers refuse already).  Waits for queued renders like
+ * the other setters.  SPT_ERR_INVALID: NULL scene or on > 1, checked before
+ * anything is touched. */
+spt_status spt_scene_set_mis(spt_scene scene, uint32_t on);
+spt_status spt_scene_get_mis(spt_scene scene, uint32_t* on);
+
 /* Host only, no device: the sampling table of an n x n octahedral image (n x n
  * x 3 floats, row j, column i; 1 <= n <= 4096).  In f64: Y = max(|r|, |g|, |b|);
  * Ybar(i, j) = sum over the 3 x 3 neighbours (octahedral edge rule) of

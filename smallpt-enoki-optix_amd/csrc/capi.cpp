@@ -1043,6 +1043,25 @@ spt_status spt_scene_get_sky_sampling(spt_scene sc, uint32_t* on, float* share, 
     return SPT_OK;
 }
 
+spt_status spt_scene_set_mis(spt_scene sc, uint32_t on) {
+    static const char* what = "spt_scene_set_mis";
+    if (!sc) return fail(SPT_ERR_INVALID, "%s: NULL scene", what);
+    if (on > 1) return fail(SPT_ERR_INVALID, "%s: on = %u (0 or 1)", what, on);
+    DeviceGuard dg(sc->device);
+    std::lock_guard<std::mutex> lk(sc->mu);
+    spt_status st = quiesce_scene(sc);  // as the other setters (a queued render took its DeviceScene by value)
+    if (st) return st;
+    sc->mis = on != 0;
+    return SPT_OK;
+}
+
+spt_status spt_scene_get_mis(spt_scene sc, uint32_t* on) {
+    if (!sc) return fail(SPT_ERR_INVALID, "spt_scene_get_mis: NULL scene");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (on) *on = sc->mis ? 1u : 0u;
+    return SPT_OK;
+}
+
 spt_status spt_sky_table_build(const float* rgb, uint32_t n, float* marginal, float* conditional, float* density,
                                uint32_t* cells_out) {
     static const char* what = "spt_sky_table_build";

@@ -1518,8 +1518,16 @@ __global__ __launch_bounds__(kIsectBlock) void aov_kernel(AovArgs a) {
 // where the scene samples its triangles too (a.sc.lights), toward one of them
 // with probability 1 - share.  Bit 1 of park[1].z: "the next escape adds no
 // sky"; bit 0 (the triangles' bit) is set only where the triangles are sampled.
+//
+// kMis (with kNee): the scene combines its shadow rays and its bounce rays
+// with the balance heuristic (DeviceScene::mis).  The same
+// rays; a shadow ray's contribution carries the factor cx / (cx + s c*)
+// instead of cx / (s c*), and what the two bits dropped is added with the
+// weight cb / (cb + s c*) instead — cb, the bounce sampler's own density
+// toward the bounce ray, waits in park[1].w from the vertex to the path's
+// next shade.
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
-          bool kNee = false, bool kSky = false>
+          bool kNee = false, bool kSky = false, bool kMis = false>
 __global__ __launch_bounds__(kIsectBlock)
 __attribute__((amdgpu_waves_per_eu(kDrain && kMode == kModeUnit ? (kNt ? SPT_DRAIN_WAVES_NT : SPT_DRAIN_WAVES)
                                    : kDrain ? SPT_DRAIN_WAVES_RGB : SPT_FUSED_WAVES, 8)))
@@ -1527,6 +1535,7 @@ void render_fused_kernel(FusedArgs a) {
     constexpr bool kEmit = kMode == kModeEmit;
     static_assert(!kNee || (kEmit && !kDrain), "light sampling: emitter mode, not the drain");
     static_assert(!kSky || (kNee && kEnv), "sky sampling: the light-sampling lane loop of a scene with a sky image");
+    static_assert(!kMis || kNee, "MIS: between the shadow rays and the bounce rays of the light-sampling lane loop");
 #if SPT_WAVE_LOG
     const unsigned long long wl_t0 = (unsigned long long)wall_clock64();
 #endif
@@ -1630,7 +1639,7 @@ void render_fused_kernel(FusedArgs a) {
                     if (vis) {
                         const float4 p0 = park[0], p1 = park[1];
                         park[0] = make_float4(p0.x, p0.y, p0.z, p0.w + p2.w);
-                        park[1] = make_float4(p1.x + p3.x, p1.y + p3.y, p1.z, 0.0f);
+                        park[1] = make_float4(p1.x + p3.x, p1.y + p3.y, p1.z, kMis ? p1.w : 0.0f);  // (kMis: cb)
                     }
                     dir = v3(p2.x, p2.y, p2.z);
                     need_init = true;
@@ -1641,10 +1650,12 @@ void render_fused_kernel(FusedArgs a) {
                 pending = false;
                 bool term = true;
                 uint32_t nee_prev = 0;  // kNee: the last vertex sampled the lights
+                float cb = 0.0f;        // kMis: the bounce sampler's density toward this ray (pi x, §16)
                 if constexpr (kPark) {
                     const float4 p0 = park[0], p1 = park[1];
                     thr = p0.x; thg = p0.y; thb = p0.z; lr = p0.w; lg = p1.x; lb = p1.y;
                     if constexpr (kNee) nee_prev = f2u(p1.z);
+                    if constexpr (kMis) cb = p1.w;
                 }
                 const uint32_t depth = meta & ((1u << kMetaDepthBits) - 1u), sample = meta >> kMetaDepthBits;
                 TraceHit hh = tr.hit(a.sc, L);
@@ -1664,6 +1675,13 @@ void render_fused_kernel(FusedArgs a) {
                             lr = lr + thr * er;                    // main.cpp:407
                             lg = lg + thg * eg;
                             lb = lb + thb * eb;
+                        } else if constexpr (kMis && kSky) {
+                            // (the sky sample and this escape share it by the balance heuristic)
+                            const float w = mis_escape_weight(cb, a.sc.lights ? a.sc.envmap->sky->share : 1.0f,
+                                                              sky_pdf(a.sc, dir));
+                            lr = lr + (thr * er) * w;
+                            lg = lg + (thg * eg) * w;
+                            lb = lb + (thb * eb) * w;
                         }
                     }
                 } else {
@@ -1674,6 +1692,17 @@ void render_fused_kernel(FusedArgs a) {
                         lr = lr + thr * a.sc.emission[mat * 3];
                         lg = lg + thg * a.sc.emission[mat * 3 + 1];
                         lb = lb + thb * a.sc.emission[mat * 3 + 2];
+                    } else if constexpr (kMis) {
+                        // (the triangle sample and this hit share it by the balance heuristic; the
+                        // bit is set only where the scene has a light table)
+                        if (mat < a.sc.nemit) {
+                            float s = 1.0f;
+                            if constexpr (kSky) s = 1.0f - a.sc.envmap->sky->share;
+                            const float w = mis_light_hit(a.sc.lights, hh.id, cb, s, dir, hh.t);
+                            lr = lr + (thr * a.sc.emission[mat * 3]) * w;
+                            lg = lg + (thg * a.sc.emission[mat * 3 + 1]) * w;
+                            lb = lb + (thb * a.sc.emission[mat * 3 + 2]) * w;
+                        }
                     }
                     if (depth + 1 < a.max_depth) {
                         // the global pixel (main.cpp:379-382), for the roulette draw and the PCG32 stream
@@ -1744,28 +1773,33 @@ void render_fused_kernel(FusedArgs a) {
                                             nee_prev = both ? 3u : 2u;
                                             float wsel = 1.0f;
                                             if (!both || sky_uniform(gpix, sample, depth, 4u) < share) {
-                                                traced = sky_sample(a.sc, nh, v3(thr, thg, thb), v3(a.env_r, a.env_g, a.env_b),
-                                                                    sky_uniform(gpix, sample, depth, 0u),
-                                                                    sky_uniform(gpix, sample, depth, 1u),
-                                                                    sky_uniform(gpix, sample, depth, 2u),
-                                                                    sky_uniform(gpix, sample, depth, 3u), sd, sc3);
+                                                traced = sky_sample<kMis>(a.sc, nh, v3(thr, thg, thb), v3(a.env_r, a.env_g, a.env_b),
+                                                                          sky_uniform(gpix, sample, depth, 0u),
+                                                                          sky_uniform(gpix, sample, depth, 1u),
+                                                                          sky_uniform(gpix, sample, depth, 2u),
+                                                                          sky_uniform(gpix, sample, depth, 3u), sd, sc3,
+                                                                          both ? share : 1.0f);
                                                 lid = kSkyLightId;
                                                 skyray = traced;
                                                 wsel = share;
                                             } else {
-                                                traced = light_sample(a.sc.lights, hp, nh, v3(thr, thg, thb),
-                                                                      light_uniform(gpix, sample, depth, 0u),
-                                                                      light_uniform(gpix, sample, depth, 1u),
-                                                                      light_uniform(gpix, sample, depth, 2u), sd, sc3, lid);
                                                 wsel = 1.0f - share;
+                                                traced = light_sample<kMis>(a.sc.lights, hp, nh, v3(thr, thg, thb),
+                                                                            light_uniform(gpix, sample, depth, 0u),
+                                                                            light_uniform(gpix, sample, depth, 1u),
+                                                                            light_uniform(gpix, sample, depth, 2u), sd, sc3, lid,
+                                                                            wsel);
                                             }
-                                            if (both) sc3 = v3(sc3.x / wsel, sc3.y / wsel, sc3.z / wsel);
+                                            // (kMis: the share is inside the weight)
+                                            if (both && !kMis) sc3 = v3(sc3.x / wsel, sc3.y / wsel, sc3.z / wsel);
                                         } else {
-                                            traced = light_sample(a.sc.lights, hp, nh, v3(thr, thg, thb),
-                                                                  light_uniform(gpix, sample, depth, 0u),
-                                                                  light_uniform(gpix, sample, depth, 1u),
-                                                                  light_uniform(gpix, sample, depth, 2u), sd, sc3, lid);
+                                            traced = light_sample<kMis>(a.sc.lights, hp, nh, v3(thr, thg, thb),
+                                                                        light_uniform(gpix, sample, depth, 0u),
+                                                                        light_uniform(gpix, sample, depth, 1u),
+                                                                        light_uniform(gpix, sample, depth, 2u), sd, sc3, lid);
                                         }
+                                        // the bounce sampler's own density toward the ray it drew
+                                        if constexpr (kMis) cb = bounce_cx(nh, dir, 1.0f / sqrtf(dot(dir, dir)));
                                         if (traced) {
                                             park[2] = make_float4(dir.x, dir.y, dir.z, sc3.x);
                                             park[3] = make_float4(sc3.y, sc3.z, u2f(lid), 0.0f);
@@ -1778,7 +1812,7 @@ void render_fused_kernel(FusedArgs a) {
                             meta++;  // the next cast
                             if constexpr (kPark) {
                                 park[0] = make_float4(thr, thg, thb, lr);
-                                park[1] = make_float4(lg, lb, kNee ? u2f(nee_prev) : 0.0f, 0.0f);
+                                park[1] = make_float4(lg, lb, kNee ? u2f(nee_prev) : 0.0f, kMis ? cb : 0.0f);
                             }
                             tr.o = hp;  // traced from here: set up below with the refilled lanes
                             need_init = true;
@@ -2507,7 +2541,7 @@ hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipSt
 }
 
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
-          bool kNee = false, bool kSky = false>
+          bool kNee = false, bool kSky = false, bool kMis = false>
 static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
     static thread_local size_t cached_lds = 0;
     static thread_local uint32_t cached = 0;
@@ -2520,7 +2554,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     (void)hipGetDevice(&dev);
     if (!cached || cached_lds != lds || cached_dev != dev) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky>,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky, kMis>,
                                                          kIsectBlock, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -2533,7 +2567,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     // (the drain's grid cannot follow its count, which is on the device)
     const uint32_t blocks = kDrain ? scaled : min(scaled, blocks_for(a.count > 0 ? a.count : 1, kIsectBlock));
     if (lanes_out) *lanes_out = blocks * kIsectBlock;
-    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky>), dim3(blocks), dim3(kIsectBlock),
+    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky, kMis>), dim3(blocks), dim3(kIsectBlock),
                        lds, s, a);
     return hipGetLastError();
 }
@@ -2544,9 +2578,17 @@ static hipError_t launch_fused_e(const FusedArgs& a, hipStream_t s, uint32_t* la
     // a scene with a light table takes the kNee instance (emitter mode, never the drain: the plan)
     if constexpr (kMode == kModeEmit && !kDrain && !kNt) {
         // a scene that samples its sky image (with or without a light table): the kSky instance
-        if (a.sc.sky && a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true, true>(a, s, lanes_out);
+        // (DeviceScene::mis chooses the kMis twin of each: §16; without a table it changes nothing)
+        if (a.sc.sky && a.sc.envmap) {
+            if (a.sc.mis) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true, true, true>(a, s, lanes_out);
+            return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true, true>(a, s, lanes_out);
+        }
         if (a.sc.lights) {
-            if (a.sc.envmap) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true>(a, s, lanes_out);
+            if (a.sc.envmap) {
+                if (a.sc.mis) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true, false, true>(a, s, lanes_out);
+                return launch_fused_t<Tr, kMode, kDrain, kNt, kList, true, true>(a, s, lanes_out);
+            }
+            if (a.sc.mis) return launch_fused_t<Tr, kMode, kDrain, kNt, kList, false, true, false, true>(a, s, lanes_out);
             return launch_fused_t<Tr, kMode, kDrain, kNt, kList, false, true>(a, s, lanes_out);
         }
     }

@@ -23,7 +23,7 @@
 //                  [--aov PREFIX] [--denoise [--denoise-iters N]]
 //                  [--passes N] [--variance FILE] [--denoise-var]
 //                  [--envmap sky.pfm [--env-res N] | --envmap-oct sky.pfm] [--env-rotate-y DEG] [--nee]
-//                  [--sky-nee [--sky-share X]]
+//                  [--sky-nee [--sky-share X]] [--mis]
 //
 // --aov PREFIX writes the first-hit buffers of the render (spt_render_aov) as
 // PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm (depth in all three
@@ -60,6 +60,10 @@
 // vertex); it needs --envmap or --envmap-oct and is refused without one.
 // --sky-share X (default 0.5, inside (0, 1)) is the probability of the sky
 // where --nee samples the emissive triangles too.
+//
+// --mis combines those shadow rays with the bounce rays by the balance
+// heuristic (spt_scene_set_mis); it needs --nee or --sky-nee and is refused
+// without either.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -109,7 +113,7 @@ struct Rank {
 // host.  The scene is committed on each device (or loaded from the cache).
 void render_multi(const std::string& path, const spt::Mesh* mesh, spt_render_params p, int ngpu, bool shared,
                   uint32_t rows_per_group, std::vector<float>& image, spt_render_stats& total, double& ms,
-                  bool nee = false) {
+                  bool nee = false, bool mis = false) {
     int ndev = 0;
     hip_check(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
     if (!shared && ngpu > ndev)
@@ -148,6 +152,7 @@ void render_multi(const std::string& path, const spt::Mesh* mesh, spt_render_par
         if (mesh) k.scene.commit_from(*mesh, k.device);
         else k.scene.load(path, k.device);
         if (nee) k.scene.set_light_sampling();  // every rank's own table: the same triangles, the same table
+        if (mis) k.scene.set_mis();
         hip_check(hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking), "hipStreamCreate");
         hip_check(hipEventCreateWithFlags(&k.done, hipEventDisableTiming), "hipEventCreate");
         hip_check(hipMalloc((void**)&k.tile, sizeof(float) * count), "hipMalloc tile");
@@ -256,6 +261,7 @@ int main(int argc, char** argv) {
     bool nee = false;           // --nee: spt_scene_set_light_sampling
     bool sky_nee = false, set_sky_share = false;  // --sky-nee: spt_scene_set_sky_sampling
     float sky_share = 0.5f;     // --sky-share
+    bool mis = false;           // --mis: spt_scene_set_mis
     int denoise_iters = -1;  // -1: spt_default_denoise_params
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
@@ -298,6 +304,7 @@ int main(int argc, char** argv) {
         else if (a == "--env-rotate-y") { env_rotate_y = std::atof(next()); env_rotate = true; }
         else if (a == "--nee") nee = true;
         else if (a == "--sky-nee") sky_nee = true;
+        else if (a == "--mis") mis = true;
         else if (a == "--sky-share") { sky_share = (float)std::atof(next()); set_sky_share = true; }
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
@@ -339,6 +346,10 @@ int main(int argc, char** argv) {
     }
     if ((set_sky_share && !sky_nee) || !(sky_share > 0.0f && sky_share < 1.0f)) {
         std::cerr << "--sky-share takes a number inside (0, 1) and goes with --sky-nee\n";
+        return 2;
+    }
+    if (mis && !nee && !sky_nee) {
+        std::cerr << "--mis weighs the shadow rays of --nee / --sky-nee against the bounce rays: it goes with one of them\n";
         return 2;
     }
     if (do_denoise && do_denoise_var) {
@@ -396,6 +407,7 @@ int main(int argc, char** argv) {
         }
         if (nee && ngpu < 1) scene.set_light_sampling();  // after the save: the cache does not store the switch
         if (sky_nee) scene.set_sky_sampling(true, sky_share);  // (a map renders on one device: this scene)
+        if (mis && ngpu < 1) scene.set_mis();
         if (pi.has_camera) {
             p.camera = pi.camera;
             if (!set_w) p.width = pi.xres;
@@ -408,7 +420,7 @@ int main(int argc, char** argv) {
         spt_render_stats st{};
         double ms = 0.0;
         if (ngpu >= 1) {
-            render_multi(obj, mesh.get(), p, ngpu, shared, rows_per_group, host, st, ms, nee);
+            render_multi(obj, mesh.get(), p, ngpu, shared, rows_per_group, host, st, ms, nee, mis);
             std::cout << ms << std::endl;  // main.cpp:431 (render + gather)
         } else {
             float* film = nullptr;

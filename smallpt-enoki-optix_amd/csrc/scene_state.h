@@ -104,6 +104,8 @@ struct spt_scene_t {
     bool light_sampling = false;
     spt::DeviceLights* lights = nullptr;
     uint32_t nlights = 0;
+    // MIS (spt_scene_set_mis): the switch alone; it acts where one of the two tables above is non-empty
+    bool mis = false;
     uint64_t node_bytes = 0;  // bytes behind nodes / nodes8 (spt_scene_save)
     uint32_t stack_depth = 1;
     spt_scene_stats stats{};
@@ -126,6 +128,7 @@ struct spt_scene_t {
         d.envmap = envmap;
         d.sky = sky != nullptr;
         d.lights = lights;
+        d.mis = mis ? 1u : 0u;
         return d;
     }
     void release() {

@@ -129,6 +129,8 @@ class Scene {
     void set_sky_sampling(bool on = true, float share = 0.5f) {
         check(spt_scene_set_sky_sampling(scene_, on ? 1u : 0u, share), "spt_scene_set_sky_sampling");
     }
+    // spt_scene_set_mis: the balance heuristic between those shadow rays and the bounce rays
+    void set_mis(bool on = true) { check(spt_scene_set_mis(scene_, on ? 1u : 0u), "spt_scene_set_mis"); }
     spt_refit_stats refit_stats() const {
         spt_refit_stats st{};
         check(spt_scene_get_refit_stats(scene_, &st), "spt_scene_get_refit_stats");

@@ -90,6 +90,7 @@ struct DeviceScene {
     const int32_t* orig2slot;
     const float* albedo;   // 3 per material
     uint32_t nmat;
+    uint32_t mis;          // spt_scene_set_mis: the light / sky sampling instances weigh with the balance heuristic (in the padding: the struct does not grow)
     const float* emission; // 3 per material or null (no emitters)
     uint32_t nemit;
     uint32_t stack_depth;  // LDS stack entries per lane (one word each)
@@ -201,8 +202,12 @@ SPT_HD void light_shadow_interval(V3 d, float& tmin, float& tmax) {
     tmin = kRayTmin * rl;
     tmax = 1.0f + tmin;
 }
+// kMis: the contribution is (T Le) q with the balance
+// heuristic's q = cx / (cx + s cl), cl = mis_light_cl at r2 = 1 / (rl rl), s the
+// probability with which the vertex samples the triangles; the test on g is on q.
+template <bool kMis = false>
 SPT_HD bool light_sample(const DeviceLights* lt, V3 x, V3 nf, V3 T, float xi0, float xi1, float xi2, V3& d, V3& c,
-                         uint32_t& id) {
+                         uint32_t& id, float s = 1.0f) {
     const float* cdf = light_cdf(lt);
     uint32_t lo = 0, hi = lt->n - 1u;
     while (lo < hi) {
@@ -223,17 +228,33 @@ SPT_HD bool light_sample(const DeviceLights* lt, V3 x, V3 nf, V3 T, float xi0, f
     const float rl = 1.0f / sqrtf(dot(d, d));
     const float tmin = kRayTmin * rl;
     if (!(tmin <= 1.0f)) return false;
-    const Frame fr = frame_from_normal(nf);
-    const V3 c1 = cross(fr.by, fr.bz), c2 = cross(fr.bz, fr.bx), c3 = cross(fr.bx, fr.by);
-    const float det = dot(fr.bx, c1);
-    const V3 v = v3(dot(d, c1), dot(d, c2), dot(d, c3));
-    const float vv = dot(v, v);
-    const float cx = ((v.y * det) * fabsf(det)) / ((vv * vv) * ((rl * rl) * rl));
+    const float cx = bounce_cx(nf, d, rl);
     const float cy = fabsf(dot(v3(q2.y, q2.z, q2.w), d)) * rl;
-    const float g = (((cx * cy) * rl) * rl) / (kPi * q3.w);
+    float g;
+    if constexpr (kMis) g = mis_shadow_factor(cx, s * mis_light_cl(q3.w, 1.0f / (rl * rl), cy));
+    else g = (((cx * cy) * rl) * rl) / (kPi * q3.w);
     if (!(cx > 0.0f) || !(cy > 0.0f) || !(g < INFINITY)) return false;
     c = v3((T.x * q3.x) * g, (T.y * q3.y) * g, (T.z * q3.z) * g);
     return c.x != 0.0f || c.y != 0.0f || c.z != 0.0f;
+}
+
+// MIS: the weight of the emission a bounce ray d (as traced,
+// met at parameter t) finds on the triangle with the original id `id`, cb and
+// s as in mis_light_hit_weight.  The member's record is found by a binary
+// search of the ids (ascending); a triangle the table does not hold counts
+// in full.
+SPT_HD float mis_light_hit(const DeviceLights* lt, uint32_t id, float cb, float s, V3 d, float t) {
+    const uint32_t* ids = light_ids(lt);
+    uint32_t lo = 0, hi = lt->n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (id <= ids[mid]) hi = mid;
+        else lo = mid + 1u;
+    }
+    if (ids[lo] != id) return 1.0f;
+    const float4* r = light_recs(lt) + (size_t)lo * 4u;
+    const float4 q2 = r[2];
+    return mis_light_hit_weight(cb, s, v3(q2.y, q2.z, q2.w), r[3].w, d, t);
 }
 
 // The sky image's sampling table on the device (sky_table.h):
@@ -276,8 +297,11 @@ SPT_HD float sky_pdf(const DeviceScene& sc, V3 d) {
 // cx, of the normal nf as the sampler takes it).  False: no shadow ray (cx or
 // the density not positive, g not finite, or c = 0 in every channel).  f32,
 // every operation rounded, in this order: tests/sky_ref.py restates it.
+// kMis: g is the balance heuristic's q = cx / (cx + s pi sky_pdf(d)),
+// s the probability with which the vertex samples the sky.
+template <bool kMis = false>
 SPT_HD bool sky_sample(const DeviceScene& sc, V3 nf, V3 T, V3 env, float xi0, float xi1, float xi2, float xi3, V3& d,
-                       V3& c) {
+                       V3& c, float s = 1.0f) {
     const DeviceEnvMap& m = *sc.envmap;
     const float* marg = sky_marg(m.sky);
     const uint32_t j = sky_search(marg, m.n, xi0);
@@ -290,14 +314,11 @@ SPT_HD bool sky_sample(const DeviceScene& sc, V3 nf, V3 T, V3 env, float xi0, fl
            (m.rot[2] * p.x + m.rot[5] * p.y) + m.rot[8] * p.z);
     c = v3(0.0f, 0.0f, 0.0f);
     const float rl = 1.0f / sqrtf(dot(d, d));
-    const Frame fr = frame_from_normal(nf);
-    const V3 c1 = cross(fr.by, fr.bz), c2 = cross(fr.bz, fr.bx), c3 = cross(fr.bx, fr.by);
-    const float det = dot(fr.bx, c1);
-    const V3 v = v3(dot(d, c1), dot(d, c2), dot(d, c3));
-    const float vv = dot(v, v);
-    const float cx = ((v.y * det) * fabsf(det)) / ((vv * vv) * ((rl * rl) * rl));
+    const float cx = bounce_cx(nf, d, rl);
     const float pdf = sky_pdf(sc, d);
-    const float g = cx / (kPi * pdf);
+    float g;
+    if constexpr (kMis) g = mis_shadow_factor(cx, s * (kPi * pdf));
+    else g = cx / (kPi * pdf);
     if (!(cx > 0.0f) || !(pdf > 0.0f) || !(g < INFINITY)) return false;
     const V3 M = env_radiance(sc, d);
     c = v3((T.x * (env.x * M.x)) * g, (T.y * (env.y * M.y)) * g, (T.z * (env.z * M.z)) * g);

@@ -494,4 +494,60 @@ SPT_HD void light_tri_map(float xi1, float xi2, float& b1, float& b2) {
     }
 }
 
+// pi times the density with which the bounce sampler sends a ray in the
+// direction of d (any length, rl = 1 / |d|) from a vertex whose frame it builds
+// from the normal nf as it takes it: the cx of
+// light_sample and sky_sample, and the cb a bounce ray carries under MIS (§16).
+SPT_HD float bounce_cx(V3 nf, V3 d, float rl) {
+    const Frame fr = frame_from_normal(nf);
+    const V3 c1 = cross(fr.by, fr.bz), c2 = cross(fr.bz, fr.bx), c3 = cross(fr.bx, fr.by);
+    const float det = dot(fr.bx, c1);
+    const V3 v = v3(dot(d, c1), dot(d, c2), dot(d, c3));
+    const float vv = dot(v, v);
+    return ((v.y * det) * fabsf(det)) / ((vv * vv) * ((rl * rl) * rl));
+}
+
+// ------------------------------------------- multiple importance sampling
+// The balance heuristic between a vertex's shadow ray and its bounce ray
+// (DESIGN.md §16), in "pi x solid-angle density" units: c is the bounce
+// sampler's density toward the direction (bounce_cx) and sb that of the
+// shadow-ray sampler there times the probability s with which the vertex
+// chose that sampler.  f32, every operation rounded, in this order:
+// tests/mis_ref.py restates it.
+//
+// pi times the area sampler's density per solid angle: a point of a light
+// with area density pdfA at squared distance r2, cy = |ng . d| / |d|.
+SPT_HD float mis_light_cl(float pdfA, float r2, float cy) { return ((kPi * pdfA) * r2) / cy; }
+
+// The factor of a shadow ray's contribution, c / (c + sb) — the sampler's
+// weight sb / (c + sb) times the c / sb its sample is weighed with, in one
+// quotient.  The caller has c > 0.  A shadow sampler that cannot produce the
+// direction (sb zero, negative or NaN) gives +inf: no shadow ray.
+SPT_HD float mis_shadow_factor(float c, float sb) { return sb > 0.0f ? c / (c + sb) : INFINITY; }
+
+// The weight of what a bounce ray finds, c / (c + sb).  1 where the shadow-ray
+// sampler cannot produce the direction: c not positive (it refuses cx <= 0) or
+// sb zero, negative or NaN.  0 where the sum is not finite (the shadow-ray
+// sampler's weight is then 1 and its factor 0).
+SPT_HD float mis_bounce_weight(float c, float sb) {
+    if (!(c > 0.0f) || !(sb > 0.0f)) return 1.0f;
+    const float den = c + sb;
+    return den < INFINITY ? c / den : 0.0f;
+}
+
+// A bounce ray's hit on a triangle of the light table: the ray d (as traced)
+// met it at parameter t; ng and pdfA are the member's record.  A member the
+// table never draws (pdfA = 0) or seen edge-on (cy = 0, the sampler refuses it)
+// counts in full.
+SPT_HD float mis_light_hit_weight(float cb, float s, V3 ng, float pdfA, V3 d, float t) {
+    const float dd = dot(d, d);
+    const float cy = fabsf(dot(ng, d)) * (1.0f / sqrtf(dd));
+    if (!(pdfA > 0.0f) || !(cy > 0.0f)) return 1.0f;
+    return mis_bounce_weight(cb, s * mis_light_cl(pdfA, (t * t) * dd, cy));
+}
+
+// A bounce ray's escape into a sampled sky whose sampler has the solid-angle
+// density pdf in its direction (sky_pdf).
+SPT_HD float mis_escape_weight(float cb, float s, float pdf) { return mis_bounce_weight(cb, s * (kPi * pdf)); }
+
 }  // namespace spt

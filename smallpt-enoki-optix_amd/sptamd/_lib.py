@@ -47,6 +47,7 @@ EXPORTED = [
     "spt_scene_set_light_sampling", "spt_scene_get_light_sampling", "spt_light_table_build",
     "spt_scene_get_shadow_casts",
     "spt_scene_set_sky_sampling", "spt_scene_get_sky_sampling", "spt_sky_table_build",
+    "spt_scene_set_mis", "spt_scene_get_mis",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -279,6 +280,8 @@ def _load() -> ctypes.CDLL:
         "spt_light_table_build": (i32, [vp, vp, u64, vp, u32, vp, vp, vp, u32, vp]),
         "spt_scene_set_sky_sampling": (i32, [vp, u32, ctypes.c_float]),
         "spt_scene_get_sky_sampling": (i32, [vp, vp, vp, vp]),
+        "spt_scene_set_mis": (i32, [vp, u32]),
+        "spt_scene_get_mis": (i32, [vp, vp]),
         "spt_sky_table_build": (i32, [vp, u32, vp, vp, vp, vp]),
         "spt_pfm_read": (i32, [c_char_p, POINTER(POINTER(ctypes.c_float)), POINTER(u32), POINTER(u32)]),
         "spt_pfm_free": (None, [POINTER(ctypes.c_float)]),

@@ -269,6 +269,19 @@ class HipBackend:
               "spt_scene_get_sky_sampling")
         return bool(on.value), float(share.value), int(n.value)
 
+    def set_mis(self, on=True) -> None:
+        """spt_scene_set_mis: combine the shadow rays of set_light_sampling /
+        set_sky_sampling with the bounce rays by the balance heuristic instead of
+        letting them replace the bounce ray's view of those lights.  No ray more or
+        less; inert where neither table is non-empty."""
+        check(lib.spt_scene_set_mis(self._scene, 1 if on else 0), "spt_scene_set_mis")
+
+    def mis(self) -> bool:
+        """The switch of set_mis."""
+        on = ctypes.c_uint32(0)
+        check(lib.spt_scene_get_mis(self._scene, ctypes.byref(on)), "spt_scene_get_mis")
+        return bool(on.value)
+
     def set_texture(self, material: int, image=None) -> None:
         """Material `material`'s reflectance image (ImageTexture, main.cpp:34-80):
         (H, W, 3) float32, or None to remove it."""
