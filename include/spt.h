@@ -84,10 +84,14 @@ enum {
                                       the tile has at most fused_max_paths paths, 2^20 by default,
                                       or at most wavefront_paths when that is set) */
     SPT_FLAG_TIMING_ALL = 16u,     /* with SPT_FLAG_TIMING: also shade / refill / resolve launches */
-    SPT_FLAG_NO_BOUNCE_CULL = 32u  /* the camera-cast kernel (spt_config.lockstep_first = 3) queues every
+    SPT_FLAG_NO_BOUNCE_CULL = 32u, /* the camera-cast kernel (spt_config.lockstep_first = 3) queues every
                                       bounce ray: without it a bounce ray that misses every child of the
                                       BVH root ends there (spt_render_stats.culled_paths) instead of in
                                       the drain.  The image and the work counters do not depend on it */
+    SPT_FLAG_NO_ROOT_HANDOFF = 64u /* the drain behind a culling camera cast starts every queued ray at
+                                      the BVH root: without it the cast hands the root visit it made
+                                      for the cull over and the drain starts below the root.  The image
+                                      and every work counter are the same either way */
 };
 
 /* The render loop of main.cpp:354-429 plus the tile/wavefront knobs. */
@@ -340,7 +344,9 @@ typedef struct spt_config {
                                        render +18 %) and, in unit mode on scenes below
                                        256 MiB, its bounce rays that miss every child of the BVH
                                        root ended there (SPT_FLAG_NO_BOUNCE_CULL: not; config 1
-                                       +1.8 %); 0: the persistent isect kernel
+                                       +1.8 %) and the others' root visit handed to the drain,
+                                       which starts them below the root (SPT_FLAG_NO_ROOT_HANDOFF:
+                                       not; config 1 +1.3 %); 0: the persistent isect kernel
                                        for every cast.  Wide-BVH scenes (2 and 3; BVH2 scenes run
                                        1).  The image does not depend on it                 [0..3] */
     uint32_t fit_chunks;            /* 1: a job of more than fit_paths paths whose tile has at most
@@ -1098,6 +1104,11 @@ const char* spt_build_id(void);
  * (spt_render_stats.fit_retries) deterministically, without exhausting the
  * device. */
 void spt_debug_fail_workspace_alloc(int32_t nth);
+/* Test hook: how many drain launches this process has queued, in any scene, as
+ * the instance that starts every queued ray below the BVH root from the camera
+ * cast's root word (the root hand-off, SPT_FLAG_NO_ROOT_HANDOFF).  The image and
+ * the work counters do not tell that drain from the plain one; this does. */
+uint64_t spt_debug_root_drain_launches(void);
 
 /* ------------------------------------------------------------------ host */
 /* load_meshes (main.cpp:141-251): triangulating OBJ reader with tinyobj's

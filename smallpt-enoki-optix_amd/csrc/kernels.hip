@@ -460,7 +460,14 @@ struct Tracer8T {
     // this answers true for ends in step()'s first call with no hit.  Node 0's
     // address is wave-uniform.  Not for an empty scene (no node 0), and the
     // caller must have no analytic spheres to test after the BVH.
-    __device__ __forceinline__ bool root_misses(const DeviceScene& sc) {
+    __device__ __forceinline__ bool root_misses(const DeviceScene& sc) { return !root_visit(sc); }
+
+    // The root visit itself: the hit-children word take_hits installs there,
+    // the hit leaves' triangle bits (0..23) under the hit inner children's
+    // bits (24..31); zero exactly for a ray that misses every child.  The
+    // visit reads neither the any-hit flag nor the rotation bits, so the word
+    // is the one any tracer of this width makes for the same ray (enter_root).
+    __device__ __forceinline__ uint32_t root_visit(const DeviceScene& sc) {
         nhits = 0;
         tbase = 0;
         thits = 0;
@@ -470,9 +477,28 @@ struct Tracer8T {
         const uint4 w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3];
         if constexpr (kW == 6) visit_words6(w0, w1, w2, w3);
         else visit_words(w0, w1, w2, w3, np[4]);
-        return !(thits | (nhits & 0xff000000u));
+        return thits | (nhits & 0xff000000u);
     }
 
+    // root_visit's inverse, after init: the state step()'s first call leaves a
+    // ray in whose root visit made `word` (non-zero: the ray goes on) — the hit
+    // inner children over the root's child-group word, the hit leaves'
+    // triangles from the root's triangle base, nothing pushed (spa as init
+    // left it).  Both constants are read from node 0 (a wave-uniform address).
+    __device__ __forceinline__ void enter_root(const DeviceScene& sc, uint32_t word) {
+        const uint32_t* n0 = (const uint32_t*)sc.nodes8;
+        const uint32_t group = kW == 6 ? n0[6] & 0x00ffffffu : n0[4];  // q1.z / w1.x
+        tbase = kW == 6 ? n0[3] : n0[5];                               // q0.w / w1.y
+        nhits = (word & 0xff000000u) | group;
+        thits = word & 0x00ffffffu;
+    }
+
+    // kRoot (the drain that takes the camera cast's root words, render_fused_kernel):
+    // a lane set up here carries in thits the word its ray's root visit made,
+    // or 0 for a ray that still has to make it, and starts below the root
+    // (enter_root) or at it.  The word travels in thits so that no register
+    // stays live across the set-up for it.
+    template <bool kRoot = false>
     __device__ __forceinline__ void init(const DeviceScene& sc, V3 o_, V3 d, float tmin_, float tmax_, bool anyhit_,
                                          const Lds& L) {
         wr = woop_setup(o_, d);
@@ -487,7 +513,11 @@ struct Tracer8T {
         init_slabs(o_, d, tmin_, tmax_, wr.k);
         anyhit = anyhit_;
         tbase = 0;
-        thits = 0;
+        if constexpr (kRoot) {
+            if (thits) enter_root(sc, thits);
+        } else {
+            thits = 0;
+        }
         tbase2 = 0;
         thits2 = 0;
         done = sc.empty != 0;
@@ -1124,6 +1154,10 @@ __device__ __forceinline__ uint32_t compact_block(const ShadeArgs& a, bool emit,
 // compaction then counts the survivors after the cull (no holes in the queue
 // or its segments), so the queue atomic follows phase 2 instead of hiding
 // behind it.  Same visit, same inputs as the drain's: the same bits.
+// A survivor's visit is not thrown away either: where a.hits is set (the
+// sharded cast right before the forced drain, render.cpp) its word goes to
+// ((uint32_t*)a.hits)[j] beside queue entry j, and the drain's kRoot instance
+// starts the ray below the root (Tracer8T::enter_root).
 template <int kMode, bool kSpt, bool kNt, uint32_t kBlock, typename Src, typename CullTr = void>
 __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, const Src& src,
                                             unsigned long long* culled = nullptr) {
@@ -1136,6 +1170,8 @@ __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, cons
     // ---- phase 1: survive or terminate (the bounce inputs load alongside)
     bool emit = false;
     uint32_t pix = 0, meta = 0, kind = kMatDiffuse;
+    // (the cull instances reuse `slot` after phase 2 for the survivor's root
+    // word, see there: nothing below phase 2 may read it as the hit's slot)
     int32_t slot = -1;
     // The bounce inputs (hit, m0-m2, o, d, gpix) are read only where they were
     // set (phase 2 runs for survivors, emit); left uninitialised the compiler
@@ -1286,7 +1322,11 @@ __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, cons
         if (emit) {
             CullTr ct;
             ct.init_slabs(no, nd, kRayTmin, kRayTmax, CullTr::kNoRot);
-            gone = ct.root_misses(a.sc);
+            // the visit's word, kept for the hand-off below in `slot` (the hit's
+            // slot has no reader left in these instances; a local of its own
+            // changes the register allocation of the instances without the cull)
+            slot = (int32_t)ct.root_visit(a.sc);
+            gone = !slot;
             emit = !gone;
         }
         const uint64_t gball = __ballot(gone);
@@ -1311,6 +1351,11 @@ __device__ __forceinline__ void shade_block(const ShadeArgs& a, bool valid, cons
     }
     __syncthreads();
     if (emit) store_path<kMode, kNt>(a.out, s_wave_off[wave] + rank, no, nd, pix, meta + 1u, tr, tg, tb, lr, lg, lb);
+    // the root hand-off (a.hits: in the camera cast the hit records' idle
+    // buffer, or null): the word beside the queue entry, for the drain's
+    // kRoot instance to start the ray from
+    if constexpr (kCull)
+        if (emit && a.hits) ((uint32_t*)a.hits)[s_wave_off[wave] + rank] = (uint32_t)slot;
 }
 
 template <int kMode, bool kSpt, bool kNt = false>
@@ -1526,13 +1571,24 @@ __global__ __launch_bounds__(kIsectBlock) void aov_kernel(AovArgs a) {
 // weight cb / (cb + s c*) instead — cb, the bounce sampler's own density
 // toward the bounce ray, waits in park[1].w from the vertex to the path's
 // next shade.
+//
+// kRoot (the unit-mode, cached-queue drain of a wide-BVH scene only): the
+// forced drain behind a camera cast that culled (camera_cast_cull_kernel).
+// Every queued ray went through the root there, and the visit's word waits
+// at root[j] beside queue entry j (a.perm carries the plane: such a drain
+// never takes a sorted order, and the kernel has no SGPR to spare for another
+// pointer).  A lane that takes a queued path starts its ray below the root
+// (Tracer8T::enter_root) instead of making the same visit on the same inputs;
+// the rays a lane continues start at the root as ever.  Same state after the
+// set-up as after the other instances' first trace step, so the same bits.
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
-          bool kNee = false, bool kSky = false, bool kMis = false>
+          bool kNee = false, bool kSky = false, bool kMis = false, bool kRoot = false>
 __global__ __launch_bounds__(kIsectBlock)
 __attribute__((amdgpu_waves_per_eu(kDrain && kMode == kModeUnit ? (kNt ? SPT_DRAIN_WAVES_NT : SPT_DRAIN_WAVES)
                                    : kDrain ? SPT_DRAIN_WAVES_RGB : SPT_FUSED_WAVES, 8)))
 void render_fused_kernel(FusedArgs a) {
     constexpr bool kEmit = kMode == kModeEmit;
+    static_assert(!kRoot || (kDrain && kMode == kModeUnit && !kNt), "the root hand-off: the unit-mode cached-queue drain");
     static_assert(!kNee || (kEmit && !kDrain), "light sampling: emitter mode, not the drain");
     static_assert(!kSky || (kNee && kEnv), "sky sampling: the light-sampling lane loop of a scene with a sky image");
     static_assert(!kMis || kNee, "MIS: between the shadow rays and the bounce rays of the light-sampling lane loop");
@@ -1815,6 +1871,7 @@ void render_fused_kernel(FusedArgs a) {
                                 park[1] = make_float4(lg, lb, kNee ? u2f(nee_prev) : 0.0f, kMis ? cb : 0.0f);
                             }
                             tr.o = hp;  // traced from here: set up below with the refilled lanes
+                            if constexpr (kRoot) tr.thits = 0;  // ... from the root (Tracer8T::init)
                             need_init = true;
                             busy = true;
                             cont = true;
@@ -1876,8 +1933,9 @@ void render_fused_kernel(FusedArgs a) {
                 const uint32_t take = min((uint32_t)__popcll(idle), pool_end - pool);
                 if (kDrain && !busy && !pending && rank < take) {
                     // the next queued path (shade_kernel's reads), continued here
-                    const uint32_t j = a.perm ? a.perm[pool + rank] : pool + rank;
+                    const uint32_t j = kRoot ? pool + rank : a.perm ? a.perm[pool + rank] : pool + rank;
                     const float4 q1 = ldq<kNt>(a.q.q1 + j), q2 = ldq<kNt>(a.q.q2 + j);
+                    if constexpr (kRoot) tr.thits = a.perm[j];  // its root word (non-zero: it was queued)
                     meta = f2u(q1.w);
                     pix = f2u(q2.w);
                     dir = v3(q2.x, q2.y, q2.z);
@@ -1938,6 +1996,9 @@ void render_fused_kernel(FusedArgs a) {
                     if constexpr (kSky)
                         if (skyray) sky_shadow_interval(dir, tmn, tmx);
                     tr.init(a.sc, tr.o, dir, tmn, tmx, kSky && skyray, L);
+                } else if constexpr (kRoot) {
+                    tr.template init<true>(a.sc, tr.o, dir, kRayTmin, kRayTmax,
+                                           (meta & ((1u << kMetaDepthBits) - 1u)) + 1u >= a.max_depth, L);
                 } else {
                     tr.init(a.sc, tr.o, dir, kRayTmin, kRayTmax,
                             (meta & ((1u << kMetaDepthBits) - 1u)) + 1u >= a.max_depth && !kEmit, L);
@@ -2541,7 +2602,7 @@ hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipSt
 }
 
 template <typename Tr, int kMode, bool kDrain = false, bool kNt = false, bool kList = false, bool kEnv = false,
-          bool kNee = false, bool kSky = false, bool kMis = false>
+          bool kNee = false, bool kSky = false, bool kMis = false, bool kRoot = false>
 static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* lanes_out) {
     static thread_local size_t cached_lds = 0;
     static thread_local uint32_t cached = 0;
@@ -2554,7 +2615,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     (void)hipGetDevice(&dev);
     if (!cached || cached_lds != lds || cached_dev != dev) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky, kMis>,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky, kMis, kRoot>,
                                                          kIsectBlock, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -2567,7 +2628,7 @@ static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t s, uint32_t* la
     // (the drain's grid cannot follow its count, which is on the device)
     const uint32_t blocks = kDrain ? scaled : min(scaled, blocks_for(a.count > 0 ? a.count : 1, kIsectBlock));
     if (lanes_out) *lanes_out = blocks * kIsectBlock;
-    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky, kMis>), dim3(blocks), dim3(kIsectBlock),
+    hipLaunchKernelGGL((render_fused_kernel<Tr, kMode, kDrain, kNt, kList, kEnv, kNee, kSky, kMis, kRoot>), dim3(blocks), dim3(kIsectBlock),
                        lds, s, a);
     return hipGetLastError();
 }
@@ -2667,6 +2728,16 @@ hipError_t launch_drain(const FusedArgs& a, int mode, hipStream_t s) {
     if (mode == kModeEmit) return launch_drain_m<kModeEmit, false>(a, s);
     if (mode == kModeAlbedo) return launch_drain_m<kModeAlbedo, false>(a, s);
     return launch_drain_m<kModeUnit, false>(a, s);
+}
+
+// The forced drain behind a camera cast that culled and handed the root words
+// over (render_fused_kernel's kRoot; render.cpp run_iteration): a.perm is the
+// plane of words, one per queue slot.  Unit mode, cached queue, wide BVH.
+hipError_t launch_drain_root(const FusedArgs& a, hipStream_t s) {
+    if (!a.sc.nodes8 || a.sc.empty || a.nt || !a.perm || !a.seg_count) return hipErrorInvalidValue;
+    if (a.sc.node6)
+        return launch_fused_t<Tracer6F, kModeUnit, true, false, false, false, false, false, false, true>(a, s, nullptr);
+    return launch_fused_t<Tracer8F, kModeUnit, true, false, false, false, false, false, false, true>(a, s, nullptr);
 }
 
 template <typename Tr>

@@ -317,6 +317,8 @@ hipError_t create_sub_stream(hipStream_t* s, bool own_queue) {
     return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
 
+// spt_debug_root_drain_launches: drains queued through launch_drain_root
+std::atomic<uint64_t> g_root_drain_launches{0};
 // spt_debug_fail_workspace_alloc: the allocation that fails once (-1: none)
 std::atomic<int32_t> g_fail_ws_alloc{-1};
 hipError_t ws_malloc(void** p, size_t bytes) {
@@ -811,6 +813,8 @@ struct SubRun {
     bool live;
     uint64_t started, sub_begin, sub_end;  // work items known started; the share
     bool lock0;            // the first cast runs in lockstep
+    bool root_words;       // the camera cast left its survivors' root-visit words in the hit records'
+                           // buffer for the forced drain that comes next (RenderPlan::root_handoff)
 };
 
 // What the pieces of one enqueue share.
@@ -1070,6 +1074,7 @@ spt_status first_refill(RenderJob& j, SubRun& r, int k, uint32_t s0, uint32_t ns
     // enough that the isect and shade run (not the drain) — in the
     // one-lane-per-ray kernel (launch_isect_lockstep)
     r.lock0 = j.cfg().lockstep_first && pl.fit && pl.drain_on && !pl.trav_stats && first >= r.drain_T;
+    r.root_words = false;
     // (the camera cast makes these paths itself: the refill only keeps the books)
     r.ra.book_only = r.lock0 && pl.cam_cast ? 1u : 0u;
     spt_status st;
@@ -1130,7 +1135,13 @@ spt_status run_iteration(RenderJob& j, SubRun& r, int k, uint64_t it) {
         // slots behind the other working set's persistent drain, 0.4 ms on
         // the 1/8 tile, profiles/r06_exp/tile8_trace/)
         r.da.count_queue = 1;
-        if ((st = j.mark(4, sk, [&] { return launch_drain(r.da, mode, sk); }))) return st;
+        const bool root = r.root_words;
+        r.root_words = false;
+        if (root) r.da.perm = (const uint32_t*)b.hits;
+        if ((st = j.mark(4, sk, [&] { return root ? launch_drain_root(r.da, sk) : launch_drain(r.da, mode, sk); })))
+            return st;
+        if (root) g_root_drain_launches.fetch_add(1);
+        r.da.perm = nullptr;
         r.da.count_queue = 0;
         j.drain_launches++;
         r.cur = nx;
@@ -1160,6 +1171,15 @@ spt_status run_iteration(RenderJob& j, SubRun& r, int k, uint64_t it) {
         ca.n = r.known;
         // the bounce cull (an empty scene has no root to visit, and no hit to bounce from)
         unsigned long long* const culled = pl.bounce_cull && !ca.s.sc.empty ? &j.slot.dev->culled[0][0] : nullptr;
+        // the root hand-off: this cast is followed at once by the sharded drain
+        // of a cached queue.  The hit records are idle on this path (16 B per
+        // slot); a survivor's word goes to the slot of its queue entry, and the
+        // shards' segments together are the cast's r.known <= cap slots
+        r.root_words = sharded && culled && pl.root_handoff && !r.da.nt;
+        if (r.root_words) {
+            assert((uint64_t)shard_base(kShards, r.known, kIsectBlock) * sizeof(uint32_t) <= kHitBytes * (uint64_t)b.cap);
+            ca.s.hits = (const float4*)b.hits;
+        }
         if ((st = j.mark(1, sk, [&] { return launch_camera_cast(ca, mode, sk, culled); }))) return st;
         if (sharded) {
             r.da.seg_count = &b.cnt->surv_shard[0][0];
@@ -1475,6 +1495,7 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
 extern "C" {
 
 void spt_debug_fail_workspace_alloc(int32_t nth) { g_fail_ws_alloc.store(nth < 0 ? -1 : nth); }
+uint64_t spt_debug_root_drain_launches(void) { return g_root_drain_launches.load(); }
 
 spt_status spt_render_async(spt_scene sc, const spt_render_params* pp, float* film_dev, void* caller,
                             uint64_t* ticket_out) {

@@ -124,6 +124,12 @@ struct RenderPlan {
     // emitter instances stay as they are; analytic spheres, tested after the
     // BVH, never come in unit mode), for scenes the Infinity Cache holds
     bool bounce_cull = false;
+    // ... and hands each surviving ray's root visit over to the forced drain
+    // behind it, which starts the ray below the root instead of repeating the
+    // visit (render_fused_kernel's kRoot): with the cull unless
+    // SPT_FLAG_NO_ROOT_HANDOFF.  render.cpp uses it where the culling cast is
+    // followed at once by the sharded drain of a cached queue
+    bool root_handoff = false;
 };
 
 // fit_limit: UINT64_MAX, or after a working set that could not be allocated
@@ -296,6 +302,7 @@ inline RenderPlan plan_render(const RenderPlanIn& in, uint64_t fit_limit) {
     // the plain camera cast (profiles/bounce_cull/).
     pl.bounce_cull = pl.cam_shards && !(in.flags & SPT_FLAG_NO_BOUNCE_CULL) && in.mode == 0 && in.nsph == 0 &&
                      scene_bytes < kPixelMajorMinSceneBytes;
+    pl.root_handoff = pl.bounce_cull && !(in.flags & SPT_FLAG_NO_ROOT_HANDOFF);
     return pl;
 }
 

@@ -24,6 +24,7 @@ SPT_FLAG_FUSED = 4
 SPT_FLAG_WAVEFRONT = 8
 SPT_FLAG_TIMING_ALL = 16
 SPT_FLAG_NO_BOUNCE_CULL = 32
+SPT_FLAG_NO_ROOT_HANDOFF = 64
 PCG32_DEFAULT_STATE = 0x853C49E6748FEA9B
 SPT_BUILD_AUTO, SPT_BUILD_HOST_SAH, SPT_BUILD_GPU_PLOC = 0, 1, 2
 
@@ -37,7 +38,7 @@ EXPORTED = [
     "spt_bvh_build_stats", "spt_scene_set_texture", "spt_scene_set_spheres", "spt_scene_set_material_kinds",
     "spt_scene_save", "spt_scene_load", "spt_scene_cache_info",
     "spt_scene_isect_busy_begin", "spt_scene_isect_busy_end", "spt_scene_kernel_busy",
-    "spt_debug_fail_workspace_alloc",
+    "spt_debug_fail_workspace_alloc", "spt_debug_root_drain_launches",
     "spt_render_aov", "spt_default_denoise_params", "spt_denoise_scratch_bytes", "spt_denoise",
     "spt_scene_update_geometry", "spt_scene_update_geometry_device", "spt_scene_get_refit_stats",
     "spt_render_accum", "spt_render_accum_async",
@@ -240,6 +241,7 @@ def _load() -> ctypes.CDLL:
         "spt_version": (c_char_p, []),
         "spt_build_id": (c_char_p, []),
         "spt_debug_fail_workspace_alloc": (None, [ctypes.c_int32]),
+        "spt_debug_root_drain_launches": (ctypes.c_uint64, []),
         "spt_obj_load": (i32, [c_char_p, POINTER(Mesh)]),
         "spt_mesh_free": (None, [POINTER(Mesh)]),
         "spt_pbrt_load": (i32, [c_char_p, POINTER(Mesh), POINTER(PbrtInfo)]),
