@@ -144,21 +144,21 @@ def sky_sample(table, tex, rot, env, nh, T, xi0, xi1, xi2, xi3, s):
 # ---- a render
 
 def contributions(mesh, p, albedo, emission, sky=None, nee=False, sky_on=False, share=0.5, mis=False, light_mesh=None,
-                  rows=None, count=None):
+                  rows=None, count=None, textures=None):
     """x[s] (spp, 3, rows, width) float32 of the scene `mesh` under OracleParams p.  sky: None
     (the constant p.env) or (tex, rot); nee / sky_on: the two samplers' switches; share: the
-    sky's where both tables are non-empty; mis: the switch of §16.  count: a dict that
-    receives shadow_casts and the numbers of weighted hits and escapes."""
+    sky's where both tables are non-empty; mis: the switch of §16.  textures: {material:
+    (H, W, 3) image}.  count: a dict that receives shadow_casts, the numbers of weighted
+    hits and escapes, and nee_ref.EVENTS."""
     albedo = np.asarray(albedo, F).reshape(-1, 3)
     emi = None if emission is None else np.asarray(emission, F).reshape(-1, 3)
-    osc = O.OracleScene(mesh, albedo=albedo, emission=emi)
+    osc = O.OracleScene(mesh, albedo=albedo, emission=emi, textures=textures)
     rays, ids, tuv, cnt, pix, smp, shape = R.paths(osc, p, rows)
     N, D = ids.shape
     mat_id = np.asarray(mesh["mat_id"], np.int64) if mesh.get("mat_id") is not None else np.zeros(len(mesh["pos_tri"]), np.int64)
     sph = None if mesh.get("spheres") is None else np.asarray(mesh["spheres"], F).reshape(-1, 4)
     sph_mat = None if sph is None else np.asarray(mesh["sphere_mat"], np.int64)
     kinds = np.zeros(0, np.int64) if mesh.get("kinds") is None else np.asarray(mesh["kinds"], np.int64)
-    assert not np.any(kinds == 2), "mis_ref does not restate the glass weight"
     lm = mesh if light_mesh is None else light_mesh
     ltab = R.light_table(R.tri_soup(lm), lm.get("mat_id"), emi)
     nee = bool(nee) and len(ltab[0]) > 0
@@ -178,12 +178,15 @@ def contributions(mesh, p, albedo, emission, sky=None, nee=False, sky_on=False, 
     T, L = np.ones((N, 3), F), np.zeros((N, 3), F)
     bit_tri, bit_sky, active = np.zeros(N, bool), np.zeros(N, bool), np.ones(N, bool)
     cb = np.zeros(N, F)
+    after_spec = np.zeros(N, bool)                 # the ray of this cast left a mirror or glass vertex
+    ev = dict.fromkeys(R.EVENTS, 0)
     shadow_casts = hits_w = escapes_w = 0
     for j in range(D):
         assert np.array_equal(active, cnt > j)
         idj = ids[:, j].astype(np.int64)
         dj_ray = rays[:, j, 3:6]
         miss = active & (idj == -1)
+        ev["escapes_after_specular"] += int((miss & after_spec & ~bit_sky).sum())
         if miss.any():
             Ev = np.broadcast_to(env, (N, 3))
             if sky is not None:
@@ -205,6 +208,7 @@ def contributions(mesh, p, albedo, emission, sky=None, nee=False, sky_on=False, 
             emits = hit & (m >= 0) & (m < len(emi))
             em = emits & ~(bit_tri & tri)
             L = np.where(em[:, None], (L + (T * emi[np.clip(m, 0, len(emi) - 1)]).astype(F)).astype(F), L)
+            ev["emitter_hits_after_specular"] += int((em & tri & after_spec & R.emits(emi, m)).sum())
             part = emits & bit_tri & tri & mis
             if part.any():
                 k = np.nonzero(part)[0]
@@ -216,8 +220,7 @@ def contributions(mesh, p, albedo, emission, sky=None, nee=False, sky_on=False, 
                 L[k] = (L[k] + ((T[k] * le).astype(F) * w[:, None]).astype(F)).astype(F)
                 hits_w += len(k)
         cont = hit & (j + 1 < D)
-        ma = np.where((m >= 0) & (m < len(albedo)), m, 0)
-        T = np.where(cont[:, None], (T * albedo[ma]).astype(F), T)
+        T = np.where(cont[:, None], (T * R.reflectance(mesh, textures, m, idj, tuv[:, j, 1], tuv[:, j, 2], albedo)).astype(F), T)
         if j + 1 >= p.rr_start_depth:
             q = np.max(T, axis=1)
             rr = cont & (q < 1)
@@ -226,6 +229,10 @@ def contributions(mesh, p, albedo, emission, sky=None, nee=False, sky_on=False, 
                 T = np.where((rr & ~die)[:, None], (T / q[:, None]).astype(F), T)
             cont = cont & ~die
         kind = np.where((m >= 0) & (m < len(kinds)), kinds[np.clip(m, 0, max(len(kinds) - 1, 0))] if len(kinds) else 0, 0)
+        if j + 1 < D:                              # the scatter weight: after the roulette, continuing paths only
+            sw = R.specular_weights(nrm, sph, kind, cont, idj, tuv[:, j], dj_ray, rays[:, j + 1, 0:3], rays[:, j + 1, 3:6], ev)
+            T = np.where(cont[:, None], (T * sw[:, None]).astype(F), T)
+        after_spec = cont & (kind != 0)
         diffuse = cont & (kind == 0)
         if (on or nee) and diffuse.any():
             k = np.nonzero(diffuse)[0]
@@ -267,6 +274,9 @@ def contributions(mesh, p, albedo, emission, sky=None, nee=False, sky_on=False, 
                                         tmax=np.full(len(t), np.inf, F), closest=True)[0]
                     vis = t[hid == -1]
                     L[k[ks[vis]]] = (L[k[ks[vis]]] + c[vis]).astype(F)
+                    hk = R.hit_kinds(hid, mat_id, sph_mat, kinds)
+                    ev["shadow_rays_stopped_by_specular"] += int((hk != 0).sum())
+                    ev["sky_rays_stopped_by_specular_sphere"] += int(((hk != 0) & (hid < -1)).sum())
             kt = np.nonzero(~pick_sky)[0]
             if nee and len(kt):
                 xi = [R.light_uniform(pix[k[kt]], smp[k[kt]], dj[kt], kk) for kk in range(3)]
@@ -283,10 +293,12 @@ def contributions(mesh, p, albedo, emission, sky=None, nee=False, sky_on=False, 
                     hid = osc.intersect(x[kt[t]].T.copy(), d[t].T.copy(), tmin=tmin[t], tmax=tmax[t], closest=True)[0]
                     vis = t[hid == lid[t].astype(np.int64)]
                     L[k[kt[vis]]] = (L[k[kt[vis]]] + c[vis]).astype(F)
+                    ev["shadow_rays_stopped_by_specular"] += int((R.hit_kinds(hid, mat_id, sph_mat, kinds) != 0).sum())
         bit_tri = diffuse & nee
         bit_sky = diffuse & on
         active = cont
     if count is not None:
+        count.update(ev)
         count.update(shadow_casts=shadow_casts, weighted_hits=hits_w, weighted_escapes=escapes_w)
     Sn, Rr, Wd = shape
     return np.ascontiguousarray(np.moveaxis(L.reshape(Sn, Rr, Wd, 3), -1, 1))

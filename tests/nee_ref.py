@@ -21,9 +21,13 @@ float32, one rounded operation at a time.
   emission  the hit after such a vertex adds no emission if it is a triangle
 
 The paths themselves — rays, hits, (t, u, v) — come from the oracle
-(oracle_trace_sample), the throughput is restated from the constant albedos
-and a Python rr_uniform, and a shadow ray's closest hit is oracle_intersect's
-over the same interval (tree-independent by DESIGN.md §2's rules).  contributions()
+(oracle_trace_sample), the throughput is restated from the reflectance (the
+albedo table, or the material's image through oracle.texture_eval), a Python
+rr_uniform and, after the roulette, the scatter weight of a glass vertex
+(scatter_weight: smallpt's REFR rule, the branch read off the next ray's
+direction bits), and a shadow ray's closest hit is oracle_intersect's over the
+same interval (tree-independent by DESIGN.md §2's rules).  The marks are set at
+diffuse vertices only; a mirror or glass vertex samples nothing.  contributions()
 returns the per-sample x_s for accum_ref.moments."""
 import ctypes
 
@@ -125,7 +129,7 @@ def dot(a, b):
 def normalize(v):
     with np.errstate(all="ignore"):
         inv = (F(1) / np.sqrt(dot(v, v)).astype(F)).astype(F)
-    return (v * inv[..., None]).astype(F)
+        return (v * inv[..., None]).astype(F)
 
 
 def cross(a, b):
@@ -180,13 +184,176 @@ def light_sample(table, x, nh, T, xi0, xi1, xi2):
     return traced, d, tmin, tmax, c, ids[i]
 
 
+# ---- mirror and glass (include/spt.h SPT_MAT_MIRROR / SPT_MAT_GLASS: smallpt's SPEC and REFR)
+
+def scatter_terms(n, d_in, dtype=F):
+    """smallpt's REFR rule at unit normals n (m, 3) for incoming directions d_in, every
+    operation rounded to dtype: refl, tdir, the total-internal-reflection flag tir, cos2t,
+    Re, P and the two weights wr = Re / P, wt = Tr / (1 - P)."""
+    X = dtype
+    n, d = np.asarray(n, X), np.asarray(d_in, X)
+
+    def dt(a, b):
+        return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+    def unit(v):
+        return v * (X(1) / np.sqrt(dt(v, v)))[..., None]
+
+    with np.errstate(all="ignore"):
+        dn = unit(d)
+        ndd = dt(n, dn)
+        refl = dn - n * (X(2) * ndd)[..., None]
+        into = ndd < 0
+        nl = np.where(into[..., None], n, -n)
+        nnt = np.where(into, X(1) / X(1.5), X(1.5) / X(1))
+        ddn = dt(dn, nl)
+        cos2t = X(1) - (nnt * nnt) * (X(1) - ddn * ddn)
+        tir = cos2t < 0
+        ks = np.where(into, X(1), X(-1)) * (ddn * nnt + np.sqrt(np.where(tir, X(0), cos2t)))
+        tdir = unit(dn * nnt[..., None] - n * ks[..., None])
+        R0 = (X(0.5) * X(0.5)) / (X(2.5) * X(2.5))
+        c = X(1) - np.where(into, -ddn, dt(tdir, n))
+        Re = R0 + (X(1) - R0) * ((((c * c) * c) * c) * c)
+        Tr = X(1) - Re
+        P = X(0.25) + X(0.5) * Re
+        wr, wt = Re / P, Tr / (X(1) - P)
+    out = dict(refl=refl, tdir=tdir, tir=tir, into=into, cos2t=cos2t, Re=Re, P=P, wr=wr, wt=wt)
+    assert all(v.dtype == (bool if k in ("tir", "into") else X) for k, v in out.items())
+    return out
+
+
+def same_bits(a, b):
+    return np.all(np.ascontiguousarray(a, F).view(U) == np.ascontiguousarray(b, F).view(U), axis=-1)
+
+
+def scatter_weight(n, d_in, d_out, mirror=None, events=None):
+    """The weight (m,) float32 a mirror or glass vertex multiplies into the throughput: glass
+    Re / P where the path left along refl, Tr / (1 - P) along tdir, 1 at a total internal
+    reflection; mirror (mask `mirror`) 1.  d_out, the next ray's direction, is one of the
+    restated directions bit for bit, or this asserts.  events: a dict whose counts of total
+    internal reflections, Fresnel reflections and transmissions are raised."""
+    s = scatter_terms(n, d_in)
+    d_out = np.asarray(d_out, F)
+    mirror = np.zeros(len(d_out), bool) if mirror is None else np.asarray(mirror, bool)
+    is_r, is_t = same_bits(d_out, s["refl"]), same_bits(d_out, s["tdir"])
+    only_r = mirror | s["tir"]
+    assert np.all(is_r[only_r]), "a mirror or a total internal reflection leaves along refl"
+    fres = ~only_r
+    assert np.all(is_r[fres] ^ is_t[fres]), "a glass vertex leaves along exactly one of refl, tdir"
+    w = np.where(only_r, F(1), np.where(is_r, s["wr"], s["wt"])).astype(F)
+    if events is not None:
+        events["tir"] = events.get("tir", 0) + int((s["tir"] & ~mirror).sum())
+        events["fresnel_reflections"] = events.get("fresnel_reflections", 0) + int((fres & is_r).sum())
+        events["transmissions"] = events.get("transmissions", 0) + int((fres & is_t).sum())
+    return w
+
+
 # ---- a render
 
+# what contributions() counts beside shadow_casts (count=): continuing glass and mirror vertices
+# by surface, the glass vertices' three outcomes, hits on an emissive triangle and escapes
+# straight after a mirror or glass vertex (they count in full), and shadow rays whose closest
+# hit is a mirror or glass surface (sky_ref: the sky's shadow rays stopped by such a sphere)
+EVENTS = ("glass_on_triangles", "glass_on_spheres", "mirror_on_spheres", "tir", "fresnel_reflections", "transmissions",
+          "emitter_hits_after_specular", "escapes_after_specular", "shadow_rays_stopped_by_specular",
+          "sky_rays_stopped_by_specular_sphere")
+
+
+def emits(emi, m):
+    """The material m has a non-zero row in the emission table."""
+    return (m >= 0) & (m < len(emi)) & np.any(emi[np.clip(m, 0, len(emi) - 1)] != 0, axis=-1)
+
+
+def hit_kinds(hid, mat_id, sph_mat, kinds):
+    """The material kind at each hit id (0 at a miss, and without a kinds table)."""
+    hid = np.asarray(hid, np.int64)
+    m = np.where(hid >= 0, mat_id[np.clip(hid, 0, max(len(mat_id) - 1, 0))] if len(mat_id) else 0, -1)
+    if sph_mat is not None:
+        m = np.where(hid < -1, sph_mat[np.clip(-2 - hid, 0, len(sph_mat) - 1)], m)
+    if len(kinds) == 0:
+        return np.zeros(len(hid), np.int64)
+    return np.where((hid != -1) & (m >= 0) & (m < len(kinds)), kinds[np.clip(m, 0, len(kinds) - 1)], 0)
+
+
 def shading_normals(mesh):
-    """(T, 3, 3): the three vertex normals of every triangle, as the scene stores them."""
-    nt = np.asarray(mesh["nrm_tri"]).reshape(-1, 3)
-    assert nt.min() >= 0, "nee_ref: every triangle carries vertex normals"
-    return np.asarray(mesh["nrm"], F)[nt]
+    """(T, 3, 3): the three vertex normals of every triangle, as the scene stores them — a
+    vertex without one (index -1 or past the array, or a mesh without nrm_tri) takes
+    normalize(cross(v1 - v0, v2 - v0)) in float32."""
+    tv = tri_soup(mesh).reshape(-1, 3, 3)
+    g = normalize(cross((tv[:, 1] - tv[:, 0]).astype(F), (tv[:, 2] - tv[:, 0]).astype(F)))
+    out = np.repeat(g[:, None, :], 3, axis=1).astype(F)
+    if mesh.get("nrm_tri") is None or mesh.get("nrm") is None:
+        return out
+    nt = np.asarray(mesh["nrm_tri"], np.int64).reshape(-1, 3)
+    nrm = np.asarray(mesh["nrm"], F).reshape(-1, 3)
+    ok = (nt >= 0) & (nt < len(nrm))
+    return np.where(ok[..., None], nrm[np.clip(nt, 0, max(len(nrm) - 1, 0))], out).astype(F)
+
+
+def texcoords(mesh):
+    """(T, 3, 2) float32: the three texcoords of every triangle, (0, 0) where missing; None
+    for a mesh without them."""
+    if mesh.get("tc_tri") is None or mesh.get("tc") is None:
+        return None
+    tt = np.asarray(mesh["tc_tri"], np.int64).reshape(-1, 3)
+    tc = np.asarray(mesh["tc"], F).reshape(-1, 2)
+    ok = (tt >= 0) & (tt < len(tc))
+    return np.where(ok[..., None], tc[np.clip(tt, 0, max(len(tc) - 1, 0))], F(0)).astype(F)
+
+
+def reflectance(mesh, textures, m, id, u, v, albedo=None):
+    """(n, 3) float32: what a bounce at hit `id` (>= 0 a triangle, < -1 a sphere) with
+    barycentrics (u, v) and material m multiplies into the throughput — the material's
+    image (textures: {material: (H, W, 3)}) at the texcoord (w c0 + u c1) + v c2, w = (1 - u) - v,
+    (0, 0) on a sphere or a mesh without texcoords; else albedo[m], an m past the table taking
+    row 0.  albedo: default mesh["albedo"]."""
+    albedo = np.asarray(mesh["albedo"] if albedo is None else albedo, F).reshape(-1, 3)
+    m, id = np.asarray(m, np.int64), np.asarray(id, np.int64)
+    out = albedo[np.where((m >= 0) & (m < len(albedo)), m, 0)].astype(F)
+    if not textures:
+        return out
+    tc = texcoords(mesh)
+    u, v = np.asarray(u, F), np.asarray(v, F)
+    w = ((F(1) - u).astype(F) - v).astype(F)
+    for k in np.nonzero(np.isin(m, [int(t) for t in textures]) & (id != -1))[0]:
+        tu = tv = F(0)
+        if tc is not None and id[k] >= 0:
+            c = tc[id[k]]
+            tu = ((w[k] * c[0, 0]).astype(F) + (u[k] * c[1, 0]).astype(F)).astype(F) + (v[k] * c[2, 0]).astype(F)
+            tv = ((w[k] * c[0, 1]).astype(F) + (u[k] * c[1, 1]).astype(F)).astype(F) + (v[k] * c[2, 1]).astype(F)
+        out[k] = O.texture_eval(textures[int(m[k])], float(tu), float(tv))
+    return out
+
+
+def interpolated_normals(nrm, id, u, v):
+    """(w n0 + u n1) + v n2 of the hit triangles, not normalised; row 0's where id is no triangle."""
+    u, v = np.asarray(u, F), np.asarray(v, F)
+    w = ((F(1) - u).astype(F) - v).astype(F)
+    nv = nrm[np.clip(id, 0, len(nrm) - 1)] if len(nrm) else np.zeros((len(u), 3, 3), F)
+    return (((w[:, None] * nv[:, 0]).astype(F) + (u[:, None] * nv[:, 1]).astype(F)).astype(F)
+            + (v[:, None] * nv[:, 2]).astype(F)).astype(F)
+
+
+def specular_weights(nrm, sph, kind, cont, id, tuv, d_in, x_next, d_next, events=None):
+    """(N,) float32: scatter_weight of the continuing (`cont`) mirror and glass vertices of one
+    cast, 1 elsewhere.  The unit normal is normalize(sn) on a triangle and normalize(hp - c),
+    hp the next ray's origin, on a sphere.  events: counts by kind and surface are raised."""
+    sw = np.ones(len(id), F)
+    k = np.nonzero(cont & (kind != 0))[0]
+    if events is not None:
+        for name, sel in (("glass_on_triangles", (kind[k] == 2) & (id[k] >= 0)), ("glass_on_spheres", (kind[k] == 2) & (id[k] < -1)),
+                          ("mirror_on_spheres", (kind[k] != 2) & (id[k] < -1))):
+            events[name] = events.get(name, 0) + int(sel.sum())
+    if len(k) == 0:
+        return sw
+    n = normalize(interpolated_normals(nrm, id[k], tuv[k, 1], tuv[k, 2]))
+    if sph is not None:
+        c4 = sph[np.clip(-2 - id[k], 0, len(sph) - 1)]
+        n = np.where((id[k] < -1)[:, None], normalize((x_next[k] - c4[:, 0:3]).astype(F)), n).astype(F)
+    sw[k] = scatter_weight(n, d_in[k], d_next[k], mirror=kind[k] != 2, events=events)
+    if events is not None and "vertices" in events:          # a list: (n, d_in, d_out, mirror) of every cast
+        events["vertices"].append((n, d_in[k].copy(), d_next[k].copy(), kind[k] != 2))
+    return sw
 
 
 def paths(osc, p, rows=None):
@@ -209,23 +376,22 @@ def paths(osc, p, rows=None):
     return rays, ids, tuv, cnt, pix, smp, (p.spp, len(rows), p.width)
 
 
-def contributions(mesh, p, albedo, emission, light_mesh=None, sky=None, rows=None, on=True, count=None):
+def contributions(mesh, p, albedo, emission, light_mesh=None, sky=None, rows=None, on=True, count=None, textures=None):
     """x[s] (spp, 3, rows, width) float32 of the scene `mesh` (its "spheres" /
-    "sphere_mat" / "kinds" keys included; kinds: diffuse and mirror only) under
-    OracleParams p with light sampling on.  light_mesh: the mesh the table is
-    built from (default: mesh).  sky: None (the constant p.env) or (tex, rot) for
-    an environment map.  on=False: the plain estimator, restated the same way.
-    count: a dict that receives shadow_casts."""
+    "sphere_mat" / "kinds" keys included) under OracleParams p with light sampling on.
+    light_mesh: the mesh the table is built from (default: mesh).  sky: None (the
+    constant p.env) or (tex, rot) for an environment map.  on=False: the plain
+    estimator, restated the same way.  textures: {material: (H, W, 3) image}.
+    count: a dict that receives shadow_casts and the events of EVENTS."""
     albedo = np.asarray(albedo, F).reshape(-1, 3)
     emi = None if emission is None else np.asarray(emission, F).reshape(-1, 3)
-    osc = O.OracleScene(mesh, albedo=albedo, emission=emi)
+    osc = O.OracleScene(mesh, albedo=albedo, emission=emi, textures=textures)
     rays, ids, tuv, cnt, pix, smp, shape = paths(osc, p, rows)
     N, D = ids.shape
     mat_id = np.asarray(mesh["mat_id"], np.int64) if mesh.get("mat_id") is not None else np.zeros(len(mesh["pos_tri"]), np.int64)
     sph = None if mesh.get("spheres") is None else np.asarray(mesh["spheres"], F).reshape(-1, 4)
     sph_mat = None if sph is None else np.asarray(mesh["sphere_mat"], np.int64)
     kinds = np.zeros(0, np.int64) if mesh.get("kinds") is None else np.asarray(mesh["kinds"], np.int64)
-    assert not np.any(kinds == 2), "nee_ref does not restate the glass weight"
     lm = mesh if light_mesh is None else light_mesh
     table = light_table(tri_soup(lm), lm.get("mat_id"), emi)
     on = on and len(table[0]) > 0
@@ -233,11 +399,16 @@ def contributions(mesh, p, albedo, emission, light_mesh=None, sky=None, rows=Non
     env = np.array(list(p.env), F)
     T, L = np.ones((N, 3), F), np.zeros((N, 3), F)
     bit, active = np.zeros(N, bool), np.ones(N, bool)
+    after_spec = np.zeros(N, bool)                 # the ray of this cast left a mirror or glass vertex
+    ev = dict.fromkeys(EVENTS, 0)
+    if count is not None and "vertices" in count:  # a list that receives every mirror and glass vertex
+        ev["vertices"] = count["vertices"]
     shadow_casts = 0
     for j in range(D):
         assert np.array_equal(active, cnt > j)
         idj = ids[:, j].astype(np.int64)
         miss = active & (idj == -1)
+        ev["escapes_after_specular"] += int((miss & after_spec).sum())
         if miss.any():
             E = np.broadcast_to(env, (N, 3))
             if sky is not None:
@@ -252,9 +423,9 @@ def contributions(mesh, p, albedo, emission, light_mesh=None, sky=None, rows=Non
         if emi is not None:
             em = hit & (m >= 0) & (m < len(emi)) & ~(bit & tri)
             L = np.where(em[:, None], (L + (T * emi[np.clip(m, 0, len(emi) - 1)]).astype(F)).astype(F), L)
+            ev["emitter_hits_after_specular"] += int((em & tri & after_spec & emits(emi, m)).sum())
         cont = hit & (j + 1 < D)
-        ma = np.where((m >= 0) & (m < len(albedo)), m, 0)
-        T = np.where(cont[:, None], (T * albedo[ma]).astype(F), T)
+        T = np.where(cont[:, None], (T * reflectance(mesh, textures, m, idj, tuv[:, j, 1], tuv[:, j, 2], albedo)).astype(F), T)
         if j + 1 >= p.rr_start_depth:
             q = np.max(T, axis=1)
             rr = cont & (q < 1)
@@ -263,6 +434,11 @@ def contributions(mesh, p, albedo, emission, light_mesh=None, sky=None, rows=Non
                 T = np.where((rr & ~die)[:, None], (T / q[:, None]).astype(F), T)
             cont = cont & ~die
         kind = np.where((m >= 0) & (m < len(kinds)), kinds[np.clip(m, 0, max(len(kinds) - 1, 0))] if len(kinds) else 0, 0)
+        if j + 1 < D:                              # the scatter weight: after the roulette, continuing paths only
+            sw = specular_weights(nrm, sph, kind, cont, idj, tuv[:, j], rays[:, j, 3:6], rays[:, j + 1, 0:3],
+                                  rays[:, j + 1, 3:6], ev)
+            T = np.where(cont[:, None], (T * sw[:, None]).astype(F), T)
+        after_spec = cont & (kind != 0)
         diffuse = cont & (kind == 0)
         if on and diffuse.any():
             k = np.nonzero(diffuse)[0]
@@ -288,9 +464,11 @@ def contributions(mesh, p, albedo, emission, light_mesh=None, sky=None, rows=Non
                 hid = osc.intersect(x[t].T.copy(), d[t].T.copy(), tmin=tmin[t], tmax=tmax[t], closest=True)[0]
                 vis = t[hid == lid[t].astype(np.int64)]
                 L[k[vis]] = (L[k[vis]] + c[vis]).astype(F)
+                ev["shadow_rays_stopped_by_specular"] += int((hit_kinds(hid, mat_id, sph_mat, kinds) != 0).sum())
         bit = diffuse & on
         active = cont
     if count is not None:
+        count.update(ev)
         count["shadow_casts"] = shadow_casts
     S, R, Wd = shape
     return np.ascontiguousarray(np.moveaxis(L.reshape(S, R, Wd, 3), -1, 1))
