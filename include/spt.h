@@ -88,10 +88,15 @@ enum {
                                       bounce ray: without it a bounce ray that misses every child of the
                                       BVH root ends there (spt_render_stats.culled_paths) instead of in
                                       the drain.  The image and the work counters do not depend on it */
-    SPT_FLAG_NO_ROOT_HANDOFF = 64u /* the drain behind a culling camera cast starts every queued ray at
+    SPT_FLAG_NO_ROOT_HANDOFF = 64u, /* the drain behind a culling camera cast starts every queued ray at
                                       the BVH root: without it the cast hands the root visit it made
                                       for the cull over and the drain starts below the root.  The image
                                       and every work counter are the same either way */
+    SPT_FLAG_NO_CAMERA_ENTRY = 128u /* the camera-cast kernel starts every camera ray at the BVH root:
+                                      without it (a pinhole camera over 64-B six-wide nodes) each pixel's
+                                      rays start at the node their pixel's beam cannot avoid, from a
+                                      table built once per view.  The image and every work counter are
+                                      the same either way */
 };
 
 /* The render loop of main.cpp:354-429 plus the tile/wavefront knobs. */
@@ -1109,6 +1114,15 @@ void spt_debug_fail_workspace_alloc(int32_t nth);
  * cast's root word (the root hand-off, SPT_FLAG_NO_ROOT_HANDOFF).  The image and
  * the work counters do not tell that drain from the plain one; this does. */
 uint64_t spt_debug_root_drain_launches(void);
+/* Test hooks of the camera entry table (SPT_FLAG_NO_CAMERA_ENTRY): how many
+ * tables this process has built, in any scene — a render whose view, tile and
+ * geometry match its working set's table builds none — and a copy of the table
+ * the scene's last render used: min(capacity, n) words to `out` (one per tile
+ * pixel: the entry node's parent's child-group word in bits 0..23, its slot in
+ * bits 24..26; 0 is the root), the table's size to *n_out; 0 when that render
+ * used none.  Waits for the scene's queued renders. */
+uint64_t spt_debug_entry_builds(void);
+spt_status spt_debug_entry_table(spt_scene scene, uint32_t* out, uint32_t capacity, uint32_t* n_out);
 
 /* ------------------------------------------------------------------ host */
 /* load_meshes (main.cpp:141-251): triangulating OBJ reader with tinyobj's

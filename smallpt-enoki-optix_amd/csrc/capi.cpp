@@ -1117,6 +1117,7 @@ spt_status update_geometry_locked(spt_scene_t* sc, const RefitMeshIn& m, bool va
     RefitPlan& p = sc->refit;
     double area = 0.0;
     float ms = 0.0f;
+    sc->geom_epoch++;  // the boxes move from here on, whatever becomes of the call
     HIP_TRY(hipEventRecord(p.ev0, s));
     HIP_TRY(launch_refit_update(rs, &m, p, true, s));
     HIP_TRY(hipEventRecord(p.ev1, s));

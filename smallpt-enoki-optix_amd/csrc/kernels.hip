@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "spt_internal.h"
+#include "camera_entry.h"
 
 namespace spt {
 
@@ -354,6 +355,7 @@ constexpr float kMarginRel = 1e-6f;
 // second triangle-group slot lets a node visit ride along with any triangle
 // test while that slot is free.
 constexpr float kMinDir = 1e-20f;
+static_assert(kMarginRel == kSlabMarginRel && kMinDir == kSlabMinDir, "camera_entry.h restates the visit's constants");
 
 // The per-ray Woop constants (Sx, Sy, Sz, axis indices) and the hit record
 // (slot, u, v) live in LDS, one 16-B record each per lane after the stack
@@ -435,9 +437,11 @@ struct Tracer8T {
     // byte of oct_rep, the box bound and the hit distance.  No Woop divide,
     // nothing in LDS.  k: the Woop axis word (WoopRay::k), whose kz picks the
     // triangle records' rotation kept in oct_rep; a caller that tests no
-    // triangle passes kNoRot.  The traversal starts at the root (nhits).
+    // triangle passes kNoRot.  The traversal starts at the root (nhits), or at
+    // the inner node `entry` names (camera_entry.h: its parent's child-group
+    // word in bits 0..23, its slot in bits 24..26; 0 is the root).
     static constexpr uint32_t kNoRot = 2u << 4;
-    __device__ __forceinline__ void init_slabs(V3 o_, V3 d, float tmin_, float tmax_, uint32_t k) {
+    __device__ __forceinline__ void init_slabs(V3 o_, V3 d, float tmin_, float tmax_, uint32_t k, uint32_t entry = 0) {
         o = o_;
         const float dx = fabsf(d.x) < kMinDir ? copysignf(kMinDir, d.x) : d.x;
         const float dy = fabsf(d.y) < kMinDir ? copysignf(kMinDir, d.y) : d.y;
@@ -451,7 +455,11 @@ struct Tracer8T {
         oct_rep = oct_inv * 0x01010101u | ((kz == 2u ? 0u : kz + 1u) << 3);
         tmin = tmin_;
         tbox = box_tmin(tmin_);
-        nhits = 1u << (24u + oct_inv);  // the root: slot 0 of a virtual group at node 0
+        // entry 0, the root: slot 0 of a virtual group at node 0.  (One expression
+        // for both; the callers without an entry keep the form their code was
+        // generated from, so their kernels do not change by a single instruction.)
+        if (__builtin_constant_p(entry) && entry == 0u) nhits = 1u << (24u + oct_inv);
+        else nhits = (1u << (24u + ((entry >> 24) ^ oct_inv))) | (entry & 0x00ffffffu);
         ht = tmax_;
     }
 
@@ -497,10 +505,11 @@ struct Tracer8T {
     // a lane set up here carries in thits the word its ray's root visit made,
     // or 0 for a ray that still has to make it, and starts below the root
     // (enter_root) or at it.  The word travels in thits so that no register
-    // stays live across the set-up for it.
+    // stays live across the set-up for it.  entry: init_slabs' (the camera
+    // cast's pixels; consumed here).
     template <bool kRoot = false>
     __device__ __forceinline__ void init(const DeviceScene& sc, V3 o_, V3 d, float tmin_, float tmax_, bool anyhit_,
-                                         const Lds& L) {
+                                         const Lds& L, uint32_t entry = 0) {
         wr = woop_setup(o_, d);
         spa = (L.wbase + lane_id()) * 4u;
         *wrec(sc, L) = make_uint4(f2u(wr.Sx), f2u(wr.Sy), f2u(wr.Sz), wr.k);
@@ -510,7 +519,7 @@ struct Tracer8T {
         asm volatile("v_mov_b32 %0, -1" : "=v"(none));
         asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
         *hrec(sc, L) = make_uint4(none, none, zero, zero);
-        init_slabs(o_, d, tmin_, tmax_, wr.k);
+        init_slabs(o_, d, tmin_, tmax_, wr.k, entry);
         anyhit = anyhit_;
         tbase = 0;
         if constexpr (kRoot) {
@@ -1409,8 +1418,11 @@ __device__ __forceinline__ void camera_cast(const CameraCastArgs& a, uint32_t* l
         start_path<kList>(a.r, a.r.cursor_init + i, c.o, c.d, c.pix, c.meta);
         NoStats st;
         Tr tr;
+        // the pixel's entry node (camera_entry.h; null: the root): one word per
+        // pixel, a wave-uniform address in pixel-major order, consumed by the set-up
+        const uint32_t entry = a.entry ? a.entry[c.pix] : 0u;
         // any-hit for the last cast unless emitters need the surface (isect_queue_kernel)
-        tr.init(a.s.sc, c.o, c.d, kRayTmin, kRayTmax, a.s.max_depth <= 1 && !a.s.sc.emission, L);
+        tr.init(a.s.sc, c.o, c.d, kRayTmin, kRayTmax, a.s.max_depth <= 1 && !a.s.sc.emission, L, entry);
         if (!tr.finished())
             while (!tr.step(a.s.sc, L, st)) {
             }

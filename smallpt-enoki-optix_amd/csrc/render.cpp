@@ -91,6 +91,15 @@ struct RenderSlot {
     bool empty = false;                         // nothing was queued (an empty tile, an empty pixel list)
 };
 
+// What a camera entry table (WorkSet::entry) was built for; compared bytewise.
+struct EntryKey {
+    uint64_t geom_epoch;  // spt_scene_t::geom_epoch: a refit moves the boxes under the same pointers
+    const void* nodes;
+    uint32_t group_shift;
+    spt_camera camera;
+    uint32_t width, height, tile_index, tile_count, rows_per_group;
+};
+
 // One sub-wavefront: its own double-buffered path queue, hit records and
 // counters, driven on its own stream so its launch tails overlap the others'.
 struct Sub {
@@ -127,6 +136,15 @@ struct WorkSet {
     size_t film_cap = 0, acc_cap = 0;
     char* film = nullptr;               // per-sample contributions of a chunk (bytes or RGB floats)
     float* acc = nullptr;               // [3][P] running sum across chunks
+    // The camera entry table (camera_entry.h): one word per tile pixel, valid
+    // for entry_key — the geometry's epoch and nodes, the camera, the image
+    // and the tile.  Rebuilt on the set's stream 0 when a render's key differs
+    // (ensure_entry), so progressive passes, sample chunks and repeated frames
+    // of one view build it once.
+    uint32_t* entry = nullptr;
+    size_t entry_cap = 0;               // words
+    EntryKey entry_key{};
+    bool entry_valid = false;
     hipEvent_t fork_ev = nullptr;
     hipEvent_t free_ev = nullptr;       // recorded on the set's stream 0 after the last render that used it
     hipEvent_t call_ev = nullptr;       // the caller stream's work before a render (the render waits for it)
@@ -141,7 +159,7 @@ struct WorkSet {
             if (b.join_ev) (void)hipEventDestroy(b.join_ev);
             if (b.stream) (void)hipStreamDestroy(b.stream);
         }
-        hfree(film); hfree(acc);
+        hfree(film); hfree(acc); hfree(entry);
         if (fork_ev) (void)hipEventDestroy(fork_ev);
         if (free_ev) (void)hipEventDestroy(free_ev);
         if (call_ev) (void)hipEventDestroy(call_ev);
@@ -233,6 +251,9 @@ struct spt::Workspace {
     // spt_render_accum_list: the list check's verdict on the device and its pinned readback
     uint32_t* list_bad = nullptr;
     uint32_t* list_bad_host = nullptr;
+    // spt_debug_entry_table: the set whose camera entry table the last render read (-1: it read none), and its words
+    int entry_set = -1;
+    uint32_t entry_n = 0;
     // spt_scene_isect_busy_begin/end: every isect [0] and drain [1] launch
     // interval (scene clock) of the renders collected in between, so the union
     // across overlapping queued renders is exact (not one render's span less
@@ -319,6 +340,8 @@ hipError_t create_sub_stream(hipStream_t* s, bool own_queue) {
 
 // spt_debug_root_drain_launches: drains queued through launch_drain_root
 std::atomic<uint64_t> g_root_drain_launches{0};
+// spt_debug_entry_builds: camera entry tables built (ensure_entry)
+std::atomic<uint64_t> g_entry_builds{0};
 // spt_debug_fail_workspace_alloc: the allocation that fails once (-1: none)
 std::atomic<int32_t> g_fail_ws_alloc{-1};
 hipError_t ws_malloc(void** p, size_t bytes) {
@@ -333,7 +356,7 @@ hipError_t ws_malloc(void** p, size_t bytes) {
 }
 
 spt_status ensure_workspace(WorkSet& ws, int nsub, size_t cap, uint32_t pad, uint32_t planes, size_t film_bytes,
-                            size_t acc_floats, bool own_queues, bool drain_sort) {
+                            size_t acc_floats, bool own_queues, bool drain_sort, size_t entry_words) {
     bool quiet = !ws.used;
     const auto quiesce = [&]() -> spt_status {
         if (!quiet) HIP_TRY(hipEventSynchronize(ws.free_ev));
@@ -398,6 +421,14 @@ spt_status ensure_workspace(WorkSet& ws, int nsub, size_t cap, uint32_t pad, uin
         HIP_TRY(ws_malloc((void**)&ws.acc, sizeof(float) * acc_floats));
         ws.acc_cap = acc_floats;
     }
+    if (entry_words > ws.entry_cap) {
+        if ((st = quiesce())) return st;
+        hfree(ws.entry);
+        ws.entry_cap = 0;
+        ws.entry_valid = false;
+        HIP_TRY(ws_malloc((void**)&ws.entry, sizeof(uint32_t) * entry_words));
+        ws.entry_cap = entry_words;
+    }
     if (!ws.fork_ev) HIP_TRY(hipEventCreateWithFlags(&ws.fork_ev, hipEventDisableTiming));
     if (!ws.free_ev) HIP_TRY(hipEventCreateWithFlags(&ws.free_ev, hipEventDisableTiming));
     if (!ws.call_ev) HIP_TRY(hipEventCreateWithFlags(&ws.call_ev, hipEventDisableTiming));
@@ -420,6 +451,9 @@ spt_status release_queues(WorkSet& ws) {
     }
     hfree(ws.film);
     ws.film_cap = 0;
+    hfree(ws.entry);
+    ws.entry_cap = 0;
+    ws.entry_valid = false;
     return SPT_OK;
 }
 
@@ -758,6 +792,8 @@ RenderPlanIn plan_inputs(const spt_scene_t* sc, const spt_render_params& p, uint
     in.device_bytes = sc->stats.device_bytes;
     in.nsph = sc->nsph;
     in.wide_nodes = sc->nodes8 != nullptr;
+    in.node6 = sc->node6 != 0;
+    in.pinhole = p.camera.lens_radius == 0.0f;
     in.nee = sc->lights != nullptr || sc->sky != nullptr;
     in.null_caller = caller == nullptr || caller == hipStreamLegacy || caller == hipStreamPerThread;
     if (const WorkSet* hs = sc->ws.bound_set(caller)) {
@@ -766,6 +802,7 @@ RenderPlanIn plan_inputs(const spt_scene_t* sc, const spt_render_params& p, uint
             in.held_sub[k] = 2ull * 16 * b.planes * queue_stride(b.cap, b.pad) + kHitBytes * b.cap;
         }
         in.held_film = hs->film_cap;
+        in.held_entry = sizeof(uint32_t) * hs->entry_cap;
     }
     in.free_bytes = device_free_bytes;
     return in;
@@ -840,6 +877,7 @@ struct RenderJob {
     bool timing, timing_all;
     size_t ev = 1;            // events[0] is the origin
     uint64_t drain_launches = 0;
+    const uint32_t* entry = nullptr;  // the camera entry table of this view (ensure_entry; null: none)
 
     const spt_config& cfg() const { return sc->cfg; }
     float* sfilm() const { return (float*)ws.film; }
@@ -1160,6 +1198,7 @@ spt_status run_iteration(RenderJob& j, SubRun& r, int k, uint64_t it) {
         // refill below keeps the books as after a shade
         sharded = pl.cam_shards && !pl.drain_sort && j.forced_at(r, it + 1);
         CameraCastArgs ca;
+        ca.entry = j.entry;
         ca.r = r.ra;  // the first refill's work items (cursor_init: the share's start)
         ca.s = r.sa;
         ca.s.in = r.q[c];
@@ -1325,6 +1364,38 @@ spt_status enqueue_wavefront_chunk(RenderJob& j, SubRun* runs, uint32_t s0, uint
     return j.mark(3, stream, [&] { return j.resolve(s0, ns); });
 }
 
+// The set's camera entry table for this render's view (RenderPlan::camera_entry;
+// the buffer: ensure_workspace), built on `stream` — after the set's previous
+// render, before this one's first fork — unless the set holds the table of the
+// same geometry, camera, image and tile already.
+spt_status ensure_entry(const spt_scene_t* sc, const spt_render_params& p, uint64_t P, const Camera& cam, WorkSet& ws,
+                        hipStream_t stream) {
+    EntryKey key;
+    memset(&key, 0, sizeof(key));  // (compared bytewise: the padding too)
+    key.geom_epoch = sc->geom_epoch;
+    key.nodes = sc->nodes8;
+    key.group_shift = sc->group_shift;
+    key.camera = p.camera;
+    key.width = p.width; key.height = p.height;
+    key.tile_index = p.tile_index; key.tile_count = p.tile_count; key.rows_per_group = p.rows_per_group;
+    if (ws.entry_valid && memcmp(&key, &ws.entry_key, sizeof(key)) == 0) return SPT_OK;
+    assert(P <= ws.entry_cap);
+    ws.entry_valid = false;
+    CameraEntryArgs a{};
+    a.nodes = sc->nodes8;
+    a.group_shift = sc->group_shift;
+    a.nslots = (uint32_t)std::min<uint64_t>(sc->node_bytes / (kNode6Quads * 16), 0xffffffffull);
+    a.cam = cam;
+    a.P = (uint32_t)P; a.W = p.width;
+    a.tile_index = p.tile_index; a.tile_count = p.tile_count; a.rows_per_group = p.rows_per_group;
+    a.entry = ws.entry;
+    HIP_TRY(launch_camera_entry(a, stream));
+    ws.entry_key = key;
+    ws.entry_valid = true;
+    g_entry_builds.fetch_add(1);
+    return SPT_OK;
+}
+
 // The plan of this render and a working set that holds it: plan_render, then
 // ensure_workspace; a set that could not be allocated frees its queues and
 // the plan is made again with half the paths in flight as the limit.
@@ -1341,7 +1412,7 @@ spt_status plan_and_allocate(spt_scene_t* sc, const spt_render_params& p, uint64
         WorkSet& ws = sc->ws.pick_set(caller);
         ws.last_ticket = sc->ws.next_ticket;
         spt_status st = ensure_workspace(ws, pl.K, pl.Ck, cfg.plane_pad, in.planes, (size_t)pl.chunk * in.film_unit * P,
-                                         3 * P, pl.own_queues, pl.sort_buffers);
+                                         3 * P, pl.own_queues, pl.sort_buffers, (size_t)(pl.entry_bytes / sizeof(uint32_t)));
         if (st == SPT_ERR_OOM && !pl.fused && pl.C > kMinRetryPaths) {
             // the fit, or below it the per-cast wavefront and its film chunk, halved;
             // first the queues, hit records and film chunk this attempt allocated
@@ -1441,6 +1512,14 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
     if (ws.used) HIP_TRY(hipStreamWaitEvent(stream, ws.free_ev, 0));
     EnqueueGuard guard{ws, stream, caller, *jtab, set_idx, K};
     HIP_TRY(hipMemsetAsync(slot->dev, 0, sizeof(Stats), stream));
+    // the camera entry table, where the camera cast can run (first_refill's lock0) over a tree with a root
+    sc->ws.entry_set = -1;
+    if (pl.camera_entry && pl.fit && pl.drain_on && sc->ntri != 0 && sc->nodes8 && sc->node_bytes) {
+        if ((st = ensure_entry(sc, p, P, job.cam, ws, stream))) return st;
+        job.entry = ws.entry;
+        sc->ws.entry_set = set_idx;
+        sc->ws.entry_n = (uint32_t)P;
+    }
     // time origin for the isect launch intervals (their union = isect busy time)
     slot->timing = timing;
     if (timing) {
@@ -1496,6 +1575,23 @@ extern "C" {
 
 void spt_debug_fail_workspace_alloc(int32_t nth) { g_fail_ws_alloc.store(nth < 0 ? -1 : nth); }
 uint64_t spt_debug_root_drain_launches(void) { return g_root_drain_launches.load(); }
+uint64_t spt_debug_entry_builds(void) { return g_entry_builds.load(); }
+
+spt_status spt_debug_entry_table(spt_scene sc, uint32_t* out, uint32_t capacity, uint32_t* n_out) {
+    if (!sc || !n_out || (capacity && !out)) return fail(SPT_ERR_INVALID, "spt_debug_entry_table: NULL argument");
+    DeviceGuard dg(sc->device);
+    std::lock_guard<std::mutex> lock(sc->mu);
+    *n_out = 0;
+    const int k = sc->ws.entry_set;
+    if (k < 0) return SPT_OK;
+    const WorkSet& w = sc->ws.sets[k];
+    if (!w.entry || !w.entry_valid || sc->ws.entry_n > w.entry_cap) return SPT_OK;
+    if (w.used && w.free_ev) HIP_TRY(hipEventSynchronize(w.free_ev));
+    const uint32_t n = std::min(capacity, sc->ws.entry_n);
+    if (n) HIP_TRY(hipMemcpy(out, w.entry, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    *n_out = sc->ws.entry_n;
+    return SPT_OK;
+}
 
 spt_status spt_render_async(spt_scene sc, const spt_render_params* pp, float* film_dev, void* caller,
                             uint64_t* ticket_out) {

@@ -74,6 +74,10 @@ struct RenderPlanIn {
     uint64_t device_bytes = 0;
     uint32_t nsph = 0;
     bool wide_nodes = false;
+    // ... of 64-B six-wide nodes (bvh_build.h), and whether the render's camera
+    // is a pinhole (lens_radius 0): what the camera entry table needs
+    bool node6 = false;
+    bool pinhole = false;
     // the scene samples its emissive triangles (spt_scene_set_light_sampling with
     // a non-empty table): only the fused lane loop has that estimator, so the
     // plan is the fused pipeline whatever spt_config.pipeline, the flags and the
@@ -86,6 +90,7 @@ struct RenderPlanIn {
     // none bound): the queues and hit records per sub-wavefront, the film chunk
     uint64_t held_sub[kMaxStreams] = {};
     uint64_t held_film = 0;
+    uint64_t held_entry = 0;  // ... and the camera entry table
     // the device's free memory, asked at most once per plan and only when
     // fit_bytes is 0 and the set must grow; false: unknown
     bool (*free_bytes)(void* ctx, uint64_t* out) = nullptr;
@@ -130,6 +135,13 @@ struct RenderPlan {
     // SPT_FLAG_NO_ROOT_HANDOFF.  render.cpp uses it where the culling cast is
     // followed at once by the sharded drain of a cached queue
     bool root_handoff = false;
+    // the camera cast starts each pixel's rays at the pixel's beam's entry node
+    // instead of the root (camera_entry.h): where the camera cast runs, on a
+    // tree of 64-B six-wide nodes, under a pinhole camera, unless
+    // SPT_FLAG_NO_CAMERA_ENTRY.  The table is 4 B per tile pixel, in the working
+    // set beside the film chunk (entry_bytes)
+    bool camera_entry = false;
+    uint64_t entry_bytes = 0;
 };
 
 // fit_limit: UINT64_MAX, or after a working set that could not be allocated
@@ -204,14 +216,19 @@ inline RenderPlan plan_render(const RenderPlanIn& in, uint64_t fit_limit) {
     const bool own_queues = pl.own_queues = cfg.sub_queues != 0 && !in.null_caller;
     fit_paths = std::min<uint64_t>(cfg.fit_paths, fit_limit);
     mem_paths = fit_limit;  // paths in flight the memory allows (queues + film chunk)
+    // The camera entry table: a pure rule of the config, the tree, the camera
+    // and the flag (the render builds none for an empty scene)
+    pl.camera_entry = !fused && cfg.lockstep_first >= 2 && in.wide_nodes && in.node6 && in.pinhole &&
+                      !(in.flags & SPT_FLAG_NO_CAMERA_ENTRY);
+    pl.entry_bytes = pl.camera_entry ? 4ull * P : 0;
     if (fit_paths && !fused) {
         const uint64_t per_path = 2ull * 16 * in.planes + kHitBytes + in.film_unit;
-        const uint64_t want = std::min<uint64_t>(fit_paths, jobs) * per_path;
+        const uint64_t want = std::min<uint64_t>(fit_paths, jobs) * per_path + pl.entry_bytes;
         // what this render may reuse of the set it will get: the queues and hit
         // records of the sub-wavefronts a fitting job runs on (as allocated,
         // plane padding included) and the film chunk; a sub-wavefront beyond
         // those keeps its buffers and is not counted
-        uint64_t held = in.held_film;
+        uint64_t held = in.held_film + (pl.camera_entry ? in.held_entry : 0);
         const int kf = own_queues ? (int)cfg.fit_streams : 1;
         for (int k = 0; k < kf && k < kMaxStreams; k++) held += in.held_sub[k];
         uint64_t room = cfg.fit_bytes;

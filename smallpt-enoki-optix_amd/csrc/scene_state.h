@@ -107,6 +107,9 @@ struct spt_scene_t {
     // MIS (spt_scene_set_mis): the switch alone; it acts where one of the two tables above is non-empty
     bool mis = false;
     uint64_t node_bytes = 0;  // bytes behind nodes / nodes8 (spt_scene_save)
+    // counts the geometry's changes under the same device arrays (spt_scene_update_geometry's
+    // refit): what was derived from the boxes — the renders' camera entry tables — is keyed on it
+    uint64_t geom_epoch = 0;
     uint32_t stack_depth = 1;
     spt_scene_stats stats{};
     spt::Workspace& ws = *spt::workspace_new();

@@ -552,6 +552,18 @@ struct CameraCastArgs {
     RefillArgs r;
     ShadeArgs s;
     uint32_t n;
+    const uint32_t* entry;  // [P]: each tile pixel's entry word (camera_entry.h); null: every ray starts at the root
+};
+
+// camera_entry_kernel: the entry word of every tile pixel (camera_entry.h) of
+// a tree of 64-B nodes, one lane per pixel; nslots: the node slots behind nodes.
+struct CameraEntryArgs {
+    const uint4* nodes;
+    uint32_t group_shift, nslots;
+    Camera cam;
+    uint32_t P, W;
+    uint32_t tile_index, tile_count, rows_per_group;
+    uint32_t* entry;
 };
 // launch_camera_cast's culled (unit mode, a non-empty scene without analytic
 // spheres; null: off): a bounce ray that misses every child of the BVH root
@@ -754,6 +766,8 @@ hipError_t launch_shade(const ShadeArgs& a, int mode, uint32_t grid_items, hipSt
 // A fitting job's first cast — camera rays made, traced and shaded in one
 // launch (camera_cast_kernel); wide-BVH scenes.
 hipError_t launch_camera_cast(const CameraCastArgs& a, int mode, hipStream_t s, unsigned long long* culled = nullptr);
+// The entry table the camera cast reads (camera_entry.hip); 64-B nodes only.
+hipError_t launch_camera_entry(const CameraEntryArgs& a, hipStream_t s);
 hipError_t launch_refill(const RefillArgs& a, uint32_t grid_items, hipStream_t s);
 // The first-hit buffers of a tile (aov_kernel), every tree width.
 hipError_t launch_aov(const AovArgs& a, hipStream_t s);

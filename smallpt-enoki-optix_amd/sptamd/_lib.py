@@ -25,6 +25,7 @@ SPT_FLAG_WAVEFRONT = 8
 SPT_FLAG_TIMING_ALL = 16
 SPT_FLAG_NO_BOUNCE_CULL = 32
 SPT_FLAG_NO_ROOT_HANDOFF = 64
+SPT_FLAG_NO_CAMERA_ENTRY = 128
 PCG32_DEFAULT_STATE = 0x853C49E6748FEA9B
 SPT_BUILD_AUTO, SPT_BUILD_HOST_SAH, SPT_BUILD_GPU_PLOC = 0, 1, 2
 
@@ -39,6 +40,7 @@ EXPORTED = [
     "spt_scene_save", "spt_scene_load", "spt_scene_cache_info",
     "spt_scene_isect_busy_begin", "spt_scene_isect_busy_end", "spt_scene_kernel_busy",
     "spt_debug_fail_workspace_alloc", "spt_debug_root_drain_launches",
+    "spt_debug_entry_builds", "spt_debug_entry_table",
     "spt_render_aov", "spt_default_denoise_params", "spt_denoise_scratch_bytes", "spt_denoise",
     "spt_scene_update_geometry", "spt_scene_update_geometry_device", "spt_scene_get_refit_stats",
     "spt_render_accum", "spt_render_accum_async",
@@ -242,6 +244,8 @@ def _load() -> ctypes.CDLL:
         "spt_build_id": (c_char_p, []),
         "spt_debug_fail_workspace_alloc": (None, [ctypes.c_int32]),
         "spt_debug_root_drain_launches": (ctypes.c_uint64, []),
+        "spt_debug_entry_builds": (ctypes.c_uint64, []),
+        "spt_debug_entry_table": (i32, [vp, vp, u32, vp]),
         "spt_obj_load": (i32, [c_char_p, POINTER(Mesh)]),
         "spt_mesh_free": (None, [POINTER(Mesh)]),
         "spt_pbrt_load": (i32, [c_char_p, POINTER(Mesh), POINTER(PbrtInfo)]),
