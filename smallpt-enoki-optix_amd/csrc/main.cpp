@@ -24,6 +24,7 @@
 //                  [--passes N] [--variance FILE] [--denoise-var]
 //                  [--envmap sky.pfm [--env-res N] | --envmap-oct sky.pfm] [--env-rotate-y DEG] [--nee]
 //                  [--sky-nee [--sky-share X]] [--mis]
+//                  [--frames K --orbit-deg D [--temporal [--max-history N]]]
 //
 // --aov PREFIX writes the first-hit buffers of the render (spt_render_aov) as
 // PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm (depth in all three
@@ -39,6 +40,16 @@
 // that variance and the first-hit buffers as --denoise is (raw image to
 // <out>.raw.pfm; --denoise-iters applies); it implies the second moments.
 // Single-device too.
+//
+// --frames K renders K frames, the camera of frame k turned k x D degrees
+// (--orbit-deg D) about its up axis through look_at, and writes them as
+// <out>.000.pfm, <out>.001.pfm, ... (<out> without its .pfm).  Each frame is
+// the render of -s samples of its view, independent of the others; with
+// --temporal frame k draws samples [k s, (k + 1) s) and is blended with the
+// history reprojected from frame k - 1 (spt_temporal_accumulate; --max-history N
+// caps the history's length, default 64), and --denoise-var then filters each
+// written frame with the temporal variance (raw frames to <out>.NNN.raw.pfm).
+// Single-device; not with --passes, --adaptive, --variance, --aov or --denoise.
 //
 // --envmap FILE lights the scene with a lat-long sky image (a PFM, pbrt's
 // convention, z up), resampled to an --env-res N (default 512) octahedral map
@@ -239,6 +250,109 @@ void render_multi(const std::string& path, const spt::Mesh* mesh, spt_render_par
     }
 }
 
+// `camera` turned `degrees` about its up axis through look_at (0: the camera as it is).
+spt_camera orbit(const spt_camera& camera, double degrees) {
+    if (degrees == 0.0) return camera;
+    const double t = degrees * 3.14159265358979323846 / 180.0, c = std::cos(t), s = std::sin(t);
+    double u[3], v[3];
+    double ul = 0.0;
+    for (int k = 0; k < 3; k++) ul += (double)camera.up[k] * camera.up[k];
+    ul = std::sqrt(ul);
+    for (int k = 0; k < 3; k++) {
+        u[k] = camera.up[k] / ul;
+        v[k] = (double)camera.look_from[k] - camera.look_at[k];
+    }
+    const double uv = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
+    const double x[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+    spt_camera r = camera;  // Rodrigues: v cos + (u x v) sin + u (u.v) (1 - cos)
+    for (int k = 0; k < 3; k++) r.look_from[k] = (float)(camera.look_at[k] + (v[k] * c + x[k] * s + u[k] * uv * (1.0 - c)));
+    return r;
+}
+
+// --frames: K frames of p's view turned orbit_deg per frame, written to
+// <out>.NNN.pfm.  Without `temporal` frame k is spt_render of its view; with it,
+// the frame's own samples [k spp, (k + 1) spp) on zeroed sums, its first-hit
+// buffers, and spt_temporal_accumulate onto ping-pong histories.
+void render_frames(spt::Scene& scene, spt_render_params p, int frames, double orbit_deg, bool temporal, float max_history,
+                   bool do_denoise_var, int denoise_iters, const std::string& out, spt_render_stats& st, double& ms) {
+    const size_t npx = (size_t)p.width * p.height;
+    if ((uint64_t)p.spp * (uint64_t)frames >= (1ull << 24))
+        throw std::runtime_error("--frames x -s must stay below 2^24 samples");
+    const std::string stem = spt::ends_with(out, ".pfm") ? out.substr(0, out.size() - 4) : out;
+    const spt_camera base = p.camera;
+    spt::DeviceFloats film(3 * npx), sums(temporal ? 3 * npx : 0), sums_sq(temporal ? 3 * npx : 0);
+    // two histories (colour 3, moment 3, length 1, film 3, variance 3 planes) and two sets of guides
+    std::unique_ptr<spt::DeviceFloats> hist[2];
+    std::unique_ptr<spt::AovBuffers> aov[2];
+    spt_camera cams[2] = {base, base};
+    if (temporal)
+        for (int k = 0; k < 2; k++) {
+            hist[k].reset(new spt::DeviceFloats(13 * npx));
+            aov[k].reset(new spt::AovBuffers(npx));
+        }
+    std::vector<float> host(3 * npx);
+    for (int k = 0; k < frames; k++) {
+        p.camera = orbit(base, orbit_deg * k);
+        const auto t0 = clock_t_::now();
+        spt_render_stats fs{};
+        const float* shown = film.get();
+        const float* variance = nullptr;
+        const int cur = k & 1;
+        if (!temporal) {
+            scene.render(p, film.get(), &fs);
+        } else {
+            hip_check(hipMemset(sums.get(), 0, sizeof(float) * 3 * npx), "hipMemset sum");
+            hip_check(hipMemset(sums_sq.get(), 0, sizeof(float) * 3 * npx), "hipMemset sum_sq");
+            spt_accum acc{};
+            acc.sample_base = (uint32_t)k * p.spp;
+            acc.sum = sums.get();
+            acc.sum_sq = sums_sq.get();
+            scene.render_accum(p, acc, &fs);
+            scene.render_aov(p, aov[cur]->planes());
+            cams[cur] = p.camera;
+            spt_temporal_params tp;
+            spt_default_temporal_params(&tp);
+            tp.width = p.width;
+            tp.height = p.height;
+            tp.camera = p.camera;
+            tp.prev_camera = cams[k ? 1 - cur : cur];
+            tp.samples = (float)p.spp;
+            tp.max_history = max_history;
+            const auto history = [npx](float* b) { return spt_history{b, b + 3 * npx, b + 6 * npx}; };
+            float* const now = hist[cur]->get();
+            const spt_history h_out = history(now), h_prev = history(hist[1 - cur]->get());
+            spt::check(spt_temporal_accumulate(&tp, sums.get(), sums_sq.get(), &aov[cur]->planes(), k ? &h_prev : nullptr,
+                                               k ? &aov[1 - cur]->planes() : nullptr, &h_out, now + 7 * npx,
+                                               now + 10 * npx, nullptr),
+                       "spt_temporal_accumulate");
+            shown = now + 7 * npx;
+            variance = now + 10 * npx;
+        }
+        hip_check(hipMemcpy(host.data(), shown, sizeof(float) * 3 * npx, hipMemcpyDeviceToHost), "hipMemcpy film");
+        char num[16];
+        std::snprintf(num, sizeof(num), ".%03d", k);
+        if (do_denoise_var) {
+            spt::check(spt_pfm_write((stem + num + ".raw.pfm").c_str(), host.data(), host.data() + npx,
+                                     host.data() + 2 * npx, p.width, p.height),
+                       "spt_pfm_write");
+            spt_denoise_var_params dp;
+            spt_default_denoise_var_params(&dp);
+            dp.width = p.width;
+            dp.height = p.height;
+            if (denoise_iters >= 0) dp.iterations = (uint32_t)denoise_iters;
+            spt::DeviceFloats clean(3 * npx);
+            spt::denoise_var(dp, shown, variance, &aov[cur]->planes(), clean.get());
+            host = clean.to_host();
+        }
+        ms += ms_since(t0);
+        st.paths += fs.paths;
+        st.ray_casts += fs.ray_casts;
+        spt::check(spt_pfm_write((stem + num + ".pfm").c_str(), host.data(), host.data() + npx, host.data() + 2 * npx,
+                                 p.width, p.height),
+                   "spt_pfm_write");
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -263,6 +377,10 @@ int main(int argc, char** argv) {
     float sky_share = 0.5f;     // --sky-share
     bool mis = false;           // --mis: spt_scene_set_mis
     int denoise_iters = -1;  // -1: spt_default_denoise_params
+    int frames = 0;             // --frames: 0 = one image
+    double orbit_deg = 0.0;     // --orbit-deg, per frame
+    bool set_orbit = false, temporal = false, set_max_history = false;
+    float max_history = 64.0f;  // --max-history (spt_default_temporal_params)
     int device = 0, ngpu = 0;
     uint32_t rows_per_group = 8;
     bool shared = false;
@@ -306,6 +424,10 @@ int main(int argc, char** argv) {
         else if (a == "--sky-nee") sky_nee = true;
         else if (a == "--mis") mis = true;
         else if (a == "--sky-share") { sky_share = (float)std::atof(next()); set_sky_share = true; }
+        else if (a == "--frames") frames = std::atoi(next());
+        else if (a == "--orbit-deg") { orbit_deg = std::atof(next()); set_orbit = true; }
+        else if (a == "--temporal") temporal = true;
+        else if (a == "--max-history") { max_history = (float)std::atof(next()); set_max_history = true; }
         else if (!a.empty() && a[0] != '-') obj = a;
         else { std::cerr << "unknown flag " << a << "\n"; return 2; }
     }
@@ -360,6 +482,18 @@ int main(int argc, char** argv) {
         std::cerr << "--denoise-iters takes 0..8 and goes with --denoise / --denoise-var\n";
         return 2;
     }
+    if (frames < 0 || (frames == 0 && (set_orbit || temporal)) || (set_max_history && !temporal) ||
+        !std::isfinite(orbit_deg) || !(max_history >= 0.0f)) {
+        std::cerr << "--frames takes K >= 1; --orbit-deg and --temporal go with it, --max-history N >= 0 with --temporal\n";
+        return 2;
+    }
+    if (frames > 0 && (ngpu > 1 || passes > 0 || adaptive || !variance_out.empty() || !aov_prefix.empty() || do_denoise ||
+                       (do_denoise_var && !temporal))) {
+        std::cerr << "--frames renders on one device; not with --passes, --adaptive, --variance, --aov or --denoise, and "
+                     "--denoise-var needs --temporal\n";
+        return 2;
+    }
+    if (frames > 0 && ngpu == 1) ngpu = 0;
     // the accumulating path: asked for, or needed for the variance
     const bool accum = passes > 0 || !variance_out.empty() || do_denoise_var || adaptive;
     const bool moments = !variance_out.empty() || do_denoise_var || adaptive;
@@ -419,6 +553,15 @@ int main(int argc, char** argv) {
         std::vector<float> host(3 * npx);
         spt_render_stats st{};
         double ms = 0.0;
+        if (frames > 0) {
+            render_frames(scene, p, frames, orbit_deg, temporal, max_history, do_denoise_var, denoise_iters, out, st, ms);
+            std::cout << ms << std::endl;
+            std::cout << "wrote " << frames << " frames" << std::endl;
+            std::cout << "paths " << st.paths << " casts " << st.ray_casts << " Mpaths/s " << st.paths / (ms * 1e3)
+                      << std::endl;
+            std::cout << "done" << std::endl;
+            return 0;
+        }
         if (ngpu >= 1) {
             render_multi(obj, mesh.get(), p, ngpu, shared, rows_per_group, host, st, ms, nee, mis);
             std::cout << ms << std::endl;  // main.cpp:431 (render + gather)

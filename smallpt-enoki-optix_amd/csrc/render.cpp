@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 
+#include "camera_make.h"
 #include "render_plan.h"
 #include "scene_state.h"
 
@@ -284,37 +285,6 @@ struct spt::Workspace {
 };
 
 namespace {
-
-// ThinlensCamera constructor (pinhole.h:9-25) + the per-call constants of
-// sample_dir (pinhole.h:40-41), evaluated once on the host.
-Camera make_camera(const spt_render_params& p) {
-    const spt_camera& c = p.camera;
-    Camera cam;
-    V3 from = v3(c.look_from[0], c.look_from[1], c.look_from[2]);
-    V3 at = v3(c.look_at[0], c.look_at[1], c.look_at[2]);
-    V3 up = v3(c.up[0], c.up[1], c.up[2]);
-    cam.origin = from;
-    V3 z = normalize(at - from);
-    V3 x = normalize(cross(up, z));
-    V3 y = normalize(cross(z, x));
-    cam.frame.bx = x; cam.frame.by = y; cam.frame.bz = z;
-    cam.lens_radius = c.lens_radius;
-    cam.focal_dist = c.focal_dist;
-    cam.film_y = c.film_size_y;
-    cam.dist_lens_to_film = (c.film_size_y * 0.5f) / std::tan(c.fov_y * 0.5f);
-    cam.ratio = (float)p.width / (float)p.height;
-    cam.fw = (float)p.width;
-    cam.fh = (float)p.height;
-    // exact reciprocals of power-of-two sizes (camera_sample_dir), else 0
-    cam.inv_fw = p.width && (p.width & (p.width - 1u)) == 0u ? 1.0f / cam.fw : 0.0f;
-    cam.inv_fh = p.height && (p.height & (p.height - 1u)) == 0u ? 1.0f / cam.fh : 0.0f;
-    {
-        volatile float fz = cam.dist_lens_to_film;  // the device's operation order, no folding
-        volatile float num = cam.focal_dist * fz;
-        cam.focal_z = num / fz;
-    }
-    return cam;
-}
 
 // A set's buffers for this render; a buffer that must grow is freed only after
 // the last render that used the set has finished with it.
@@ -1507,7 +1477,8 @@ spt_status render_enqueue(spt_scene sc, const spt_render_params* pp, float* film
     const bool timing = (p.flags & SPT_FLAG_TIMING) != 0;
     RenderJob job{sc, p, pl, ws, *slot, film_dev, accum, P, A ? A : P, list_call ? list : nullptr, sample_base,
                   sample_base + p.spp, jtab->samples(),
-                  jtab->casts(), make_camera(p), stream, timing, timing && (p.flags & SPT_FLAG_TIMING_ALL) != 0};
+                  jtab->casts(), make_camera(p.camera, p.width, p.height), stream, timing,
+                  timing && (p.flags & SPT_FLAG_TIMING_ALL) != 0};
     // the set's previous render (another stream, perhaps) must be done with it
     if (ws.used) HIP_TRY(hipStreamWaitEvent(stream, ws.free_ev, 0));
     EnqueueGuard guard{ws, stream, caller, *jtab, set_idx, K};
@@ -1706,7 +1677,7 @@ spt_status spt_render_aov(spt_scene sc, const spt_render_params* pp, const spt_a
     a.spp = p.spp;
     a.rng_order = p.rng_order;
     a.tile_index = p.tile_index; a.tile_count = p.tile_count; a.rows_per_group = p.rows_per_group;
-    a.cam = make_camera(p);
+    a.cam = make_camera(p.camera, p.width, p.height);
     a.albedo_r = out->albedo_r; a.albedo_g = out->albedo_g; a.albedo_b = out->albedo_b;
     a.normal_x = out->normal_x; a.normal_y = out->normal_y; a.normal_z = out->normal_z;
     a.depth = out->depth; a.coverage = out->coverage;

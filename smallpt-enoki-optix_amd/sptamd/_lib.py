@@ -51,6 +51,7 @@ EXPORTED = [
     "spt_scene_get_shadow_casts",
     "spt_scene_set_sky_sampling", "spt_scene_get_sky_sampling", "spt_sky_table_build",
     "spt_scene_set_mis", "spt_scene_get_mis",
+    "spt_default_temporal_params", "spt_temporal_accumulate", "spt_debug_camera_constants",
 ]
 SPT_MAT_DIFFUSE, SPT_MAT_MIRROR, SPT_MAT_GLASS = 0, 1, 2
 SPT_PIPELINE_AUTO, SPT_PIPELINE_WAVEFRONT, SPT_PIPELINE_FUSED = 0, 1, 2
@@ -199,6 +200,18 @@ class Accum(ctypes.Structure):
                 ("film", c_void_p), ("variance", c_void_p)]
 
 
+class History(ctypes.Structure):
+    """spt_history: the running mean, second moment and length planes of spt_temporal_accumulate."""
+    _fields_ = [("color", c_void_p), ("moment2", c_void_p), ("length", c_void_p)]
+
+
+class TemporalParams(ctypes.Structure):
+    """spt_temporal_params: the two views and the history tests of spt_temporal_accumulate."""
+    _fields_ = [("width", c_uint32), ("height", c_uint32), ("camera", Camera), ("prev_camera", Camera),
+                ("samples", c_float), ("max_history", c_float), ("sigma_depth", c_float), ("normal_min", c_float),
+                ("reserved", c_uint32 * 2)]
+
+
 class AdaptParams(ctypes.Structure):
     """spt_adapt_params: which pixels spt_adapt_select keeps sampling."""
     _fields_ = [("min_spp", c_uint32), ("max_spp", c_uint32), ("tolerance", c_float), ("floor", c_float),
@@ -291,6 +304,10 @@ def _load() -> ctypes.CDLL:
         "spt_sky_table_build": (i32, [vp, u32, vp, vp, vp, vp]),
         "spt_pfm_read": (i32, [c_char_p, POINTER(POINTER(ctypes.c_float)), POINTER(u32), POINTER(u32)]),
         "spt_pfm_free": (None, [POINTER(ctypes.c_float)]),
+        "spt_default_temporal_params": (None, [POINTER(TemporalParams)]),
+        "spt_temporal_accumulate": (i32, [POINTER(TemporalParams), vp, vp, POINTER(Aov), POINTER(History), POINTER(Aov),
+                                          POINTER(History), vp, vp, vp]),
+        "spt_debug_camera_constants": (i32, [POINTER(Camera), u32, u32, POINTER(c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -323,6 +340,28 @@ def default_denoise_var_params() -> DenoiseVarParams:
     p = DenoiseVarParams()
     lib.spt_default_denoise_var_params(ctypes.byref(p))
     return p
+
+
+def default_temporal_params() -> TemporalParams:
+    p = TemporalParams()
+    lib.spt_default_temporal_params(ctypes.byref(p))
+    return p
+
+
+CAMERA_CONSTANTS = ("origin", "bx", "by", "bz", "lens_radius", "focal_dist", "dist_lens_to_film", "ratio", "film_y",
+                    "fw", "fh", "inv_fw", "inv_fh", "focal_z")
+
+
+def camera_constants(camera: Camera, width: int, height: int) -> dict:
+    """spt_debug_camera_constants: the constants the renders and spt_temporal_accumulate
+    derive from a view on the host, by name (origin and the frame's columns as
+    3-tuples), every value the library's f32."""
+    out = (c_float * 22)()
+    check(lib.spt_debug_camera_constants(ctypes.byref(camera), width, height, out), "spt_debug_camera_constants")
+    v = list(out)
+    res = {name: tuple(v[3 * k:3 * k + 3]) for k, name in enumerate(CAMERA_CONSTANTS[:4])}
+    res.update(zip(CAMERA_CONSTANTS[4:], v[12:]))
+    return res
 
 
 def default_adapt_params() -> AdaptParams:
@@ -432,6 +471,7 @@ __all__ = [
     "lib", "check", "SptError", "Rays", "Hits", "HitInfo", "Camera", "RenderParams", "RenderStats",
     "SceneStats", "RefitStats", "Mesh", "Config", "Aov", "AOV_PLANES", "DenoiseParams", "default_denoise_params",
     "DenoiseVarParams", "default_denoise_var_params", "Accum",
+    "History", "TemporalParams", "default_temporal_params", "camera_constants",
     "AdaptParams", "PixelList", "default_adapt_params", "default_params", "default_config", "config_from_env", "tile_rows", "EXPORTED",
     "LIB_PATH", "REPO_ROOT",
     "PCG32_DEFAULT_STATE", "SPT_RNG_Y_FIRST", "SPT_RNG_X_FIRST", "SPT_FLAG_TIMING", "c_uint8",

@@ -918,6 +918,169 @@ def denoise_var(film: torch.Tensor, variance: torch.Tensor, aov: Optional[dict] 
     return (out, vout) if return_variance else out
 
 
+def _camera_struct(camera) -> _lib.Camera:
+    """spt_camera from a dict as reference_camera's, or a copy of a _lib.Camera."""
+    if isinstance(camera, _lib.Camera):
+        return _lib.Camera.from_buffer_copy(camera)
+    return _lib.Camera.from_buffer_copy(make_params(1, 1, 1, 1, camera=camera).camera)
+
+
+def _history_struct(h: dict, shape) -> _lib.History:
+    s = _lib.History()
+    for name, sh in (("color", (3,) + shape), ("moment2", (3,) + shape), ("length", shape)):
+        t = h[name]
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == sh, \
+            f"{name}: a contiguous {sh} float32 device tensor"
+        setattr(s, name, t.data_ptr())
+    return s
+
+
+def temporal_accumulate(sum: torch.Tensor, sum_sq: torch.Tensor, aov: dict, camera, prev: Optional[dict] = None,
+                        prev_aov: Optional[dict] = None, prev_camera=None, samples: float = None,
+                        out: Optional[dict] = None, want_film: bool = True, want_variance: bool = True, stream=None,
+                        max_history: Optional[float] = None, sigma_depth: Optional[float] = None,
+                        normal_min: Optional[float] = None) -> dict:
+    """spt_temporal_accumulate: blend one frame's samples with the history of
+    the previous view (include/spt.h).  sum, sum_sq: the (3, H, W) planes of an
+    accumulation holding `samples` samples per pixel; aov: that frame's
+    render_aov dict (depth and coverage needed, normal used when both frames
+    have it); camera: the frame's view (a dict as reference_camera's, or a
+    _lib.Camera).  prev, prev_aov, prev_camera: the last call's result, guides
+    and view — all None on the first frame.  Returns a dict with color, moment2
+    ((3, H, W)), length ((H, W)) — the next call's prev — and film, variance
+    ((3, H, W), or None when not wanted); `out` supplies tensors to fill by
+    name, none of which may be a tensor of prev (history is ping-ponged).
+    max_history, sigma_depth, normal_min default to spt_default_temporal_params.
+    One launch, queued on `stream` (default: the current stream)."""
+    assert sum.is_cuda and sum.is_contiguous() and sum.dtype == torch.float32 and sum.dim() == 3 and \
+        sum.shape[0] == 3, "sum must be a contiguous (3, H, W) float32 device tensor"
+    assert sum_sq.is_cuda and sum_sq.is_contiguous() and sum_sq.dtype == torch.float32 and sum_sq.shape == sum.shape, \
+        "sum_sq: not sum's shape"
+    if samples is None:
+        raise ValueError("temporal_accumulate: samples (per pixel, in sum / sum_sq) is required")
+    if (prev is None) != (prev_aov is None) or (prev is None) != (prev_camera is None):
+        raise ValueError("temporal_accumulate: prev, prev_aov and prev_camera go together")
+    shape = tuple(sum.shape[1:])
+    p = _lib.default_temporal_params()
+    p.height, p.width = shape
+    p.camera = _camera_struct(camera)
+    p.prev_camera = _camera_struct(camera if prev_camera is None else prev_camera)
+    p.samples = float(samples)
+    for k, v in (("max_history", max_history), ("sigma_depth", sigma_depth), ("normal_min", normal_min)):
+        if v is not None:
+            setattr(p, k, float(v))
+    for guides in (aov, prev_aov):
+        for name in ("normal", "depth", "coverage"):
+            t = None if guides is None else guides.get(name)
+            assert t is None or tuple(t.shape[-2:]) == shape, f"{name}: not the image's size"
+    s = stream if stream is not None else torch.cuda.current_stream(sum.device)
+    res = {}
+    with torch.cuda.stream(s):
+        for name, sh, want in (("color", (3,) + shape, True), ("moment2", (3,) + shape, True), ("length", shape, True),
+                               ("film", (3,) + shape, want_film), ("variance", (3,) + shape, want_variance)):
+            t = None if out is None else out.get(name)
+            if t is None and want:
+                t = torch.empty(sh, dtype=torch.float32, device=sum.device)
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == sh), \
+                f"out[{name!r}]: a contiguous {sh} float32 device tensor"
+            res[name] = t if want else None
+    cur = aov_struct({k: v for k, v in aov.items() if k != "albedo"})
+    new = _history_struct(res, shape)
+    old = guides_old = None
+    if prev is not None:
+        old = ctypes.byref(_history_struct(prev, shape))
+        guides_old = ctypes.byref(aov_struct({k: v for k, v in prev_aov.items() if k != "albedo"}))
+    check(lib.spt_temporal_accumulate(ctypes.byref(p), sum.data_ptr(), sum_sq.data_ptr(), ctypes.byref(cur), old,
+                                      guides_old, ctypes.byref(new),
+                                      None if res["film"] is None else res["film"].data_ptr(),
+                                      None if res["variance"] is None else res["variance"].data_ptr(),
+                                      s.cuda_stream or None), "spt_temporal_accumulate")
+    return res
+
+
+class TemporalAccumulator:
+    """Temporal accumulation over a moving view: each frame() renders a few new
+    samples per pixel, renders the first-hit buffers of its view and blends the
+    samples with the history reprojected from the previous frame
+    (spt_temporal_accumulate; ping-pong buffers, swapped per frame).
+
+    frame(spp, camera=None) is frame k = 0, 1, ...: it sets the view if one is
+    given, renders samples [base, base + spp) of every pixel (base = the samples
+    drawn so far, k spp for a constant spp: a still camera keeps drawing new
+    samples) onto zeroed sums, and returns the render pass's stats.  film,
+    variance ((3, H, W)), length ((H, W)) and aov (render_aov's dict) are the
+    last frame's; downstream: denoise_var(t.film, t.variance, t.aov).
+    reset() drops the history (the next frame starts from its own samples; the
+    sample counter runs on).  Geometry updates between frames are allowed: a
+    surface that changed fails the depth / normal test and restarts.  Whole
+    images only (params.tile_count = 1)."""
+
+    def __init__(self, scene: "Scene", params: RenderParams, max_history: float = 64.0,
+                 sigma_depth: Optional[float] = None, normal_min: Optional[float] = None,
+                 planes: Sequence[str] = ("albedo", "normal", "depth", "coverage")):
+        if params.tile_count != 1:
+            raise ValueError("TemporalAccumulator: whole images only (tile_count = 1)")
+        if "depth" not in planes or "coverage" not in planes:
+            raise ValueError("TemporalAccumulator: planes must hold depth and coverage")
+        self.scene = scene
+        self.params = RenderParams.from_buffer_copy(params)
+        self.max_history, self.sigma_depth, self.normal_min = max_history, sigma_depth, normal_min
+        self.planes = tuple(planes)
+        shape, dev = (3, params.height, params.width), scene.backend.device
+        self.sum = torch.zeros(shape, dtype=torch.float32, device=dev)
+        self.sum_sq = torch.zeros(shape, dtype=torch.float32, device=dev)
+        new = lambda sh: torch.zeros(sh, dtype=torch.float32, device=dev)  # noqa: E731
+        self._hist = [{"color": new(shape), "moment2": new(shape), "length": new(shape[1:]), "film": new(shape),
+                       "variance": new(shape)} for _ in range(2)]
+        self._aov = [None, None]
+        self._camera = [None, None]
+        self._cur = 0            # the slot the last frame wrote
+        self.frames = 0          # frames since the last reset
+        self.samples = 0         # samples drawn per pixel over every frame: the next frame's sample_base
+
+    film = property(lambda self: self._hist[self._cur]["film"])
+    variance = property(lambda self: self._hist[self._cur]["variance"])
+    length = property(lambda self: self._hist[self._cur]["length"])
+    color = property(lambda self: self._hist[self._cur]["color"])
+    moment2 = property(lambda self: self._hist[self._cur]["moment2"])
+    aov = property(lambda self: self._aov[self._cur])
+
+    def reset(self) -> None:
+        """Drop the history: the next frame's result is its own samples."""
+        self.frames = 0
+
+    def frame(self, spp: int, camera=None, stream=None) -> dict:
+        if spp <= 0:
+            raise ValueError("TemporalAccumulator.frame: spp must be > 0")
+        if camera is not None:
+            self.params.camera = _camera_struct(camera)
+        self.params.spp = spp
+        s = stream if stream is not None else torch.cuda.current_stream(self.sum.device)
+        with torch.cuda.stream(s):
+            self.sum.zero_()
+            self.sum_sq.zero_()
+        acc, st = _lib.Accum(), RenderStats()
+        acc.sample_base = self.samples
+        acc.sum, acc.sum_sq = self.sum.data_ptr(), self.sum_sq.data_ptr()
+        self.scene.backend.sync_config()
+        check(lib.spt_render_accum(self.scene.backend.handle, ctypes.byref(self.params), ctypes.byref(acc),
+                                   ctypes.byref(st), s.cuda_stream or None), "spt_render_accum")
+        self.samples += spp
+        nxt = 1 - self._cur if self.frames else self._cur
+        self._aov[nxt] = self.scene.render_aov(self.params, self.planes, stream=s, out=self._aov[nxt])
+        self._camera[nxt] = _lib.Camera.from_buffer_copy(self.params.camera)
+        first = self.frames == 0
+        temporal_accumulate(self.sum, self.sum_sq, self._aov[nxt], self._camera[nxt],
+                            prev=None if first else self._hist[self._cur],
+                            prev_aov=None if first else self._aov[self._cur],
+                            prev_camera=None if first else self._camera[self._cur], samples=float(spp),
+                            out=self._hist[nxt], stream=s, max_history=self.max_history,
+                            sigma_depth=self.sigma_depth, normal_min=self.normal_min)
+        self._cur = nxt
+        self.frames += 1
+        return self.scene.backend._stats(st)
+
+
 def scene_cache_info(path: str) -> dict:
     """spt_scene_cache_info: checks a scene cache file (header, sizes, every
     section's checksum) without a device; returns its stats, config and extra size."""
